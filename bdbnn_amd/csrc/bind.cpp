@@ -56,6 +56,9 @@ void bdbnn_conv_dgrad(const void*, const uint32_t*, const float*, void*,
                       int, int, int, int, int, int, hipStream_t);
 int bdbnn_conv_dgrad2(const void*, const void*, const uint32_t*, void*,
                       const void*, int, int, int, int, int, hipStream_t);
+int bdbnn_conv_dgrad2_x(const void*, const void*, const void*, void*,
+                        const void*, int, float, float, int, int, int, int,
+                        int, hipStream_t);
 void bdbnn_dgrad_wdec(const uint32_t*, const float*, void*, int, int,
                       hipStream_t);
 int bdbnn_conv_wgrad2(const void*, const uint64_t*, float*, int, int, int,
@@ -759,6 +762,55 @@ at::Tensor conv_dgrad2(const at::Tensor& g, const at::Tensor& wd,
   return dx;
 }
 
+// value-mask variant for the ReAct-polynomial (mode 1) and EDE (mode 2)
+// activation gradients: the mask is evaluated from the saved bf16
+// activation x in the epilogue instead of read from a bitplane
+at::Tensor conv_dgrad2_x(const at::Tensor& g, const at::Tensor& wd,
+                         const at::Tensor& x, int64_t C, int64_t mode,
+                         double t, double k,
+                         const c10::optional<at::Tensor>& acc) {
+  TORCH_CHECK(mode == 1 || mode == 2,
+              "conv_dgrad2_x: mode must be 1 (approx) or 2 (EDE)");
+  TORCH_CHECK(g.is_cuda() && g.dim() == 4 &&
+                  g.scalar_type() == at::kBFloat16 &&
+                  g.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "conv_dgrad2_x: bf16 channels_last grad");
+  int N = (int)g.size(0), K = (int)g.size(1);
+  int H = (int)g.size(2), W = (int)g.size(3);
+  TORCH_CHECK(wd.is_cuda() && wd.dim() == 3 && wd.size(0) == 9 &&
+                  wd.size(1) == C && wd.size(2) == K &&
+                  wd.scalar_type() == at::kBFloat16 && wd.is_contiguous(),
+              "conv_dgrad2_x: decoded weights [9][C][K] bf16");
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
+                  x.scalar_type() == at::kBFloat16 &&
+                  x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "conv_dgrad2_x: bf16 channels_last activation");
+  TORCH_CHECK(x.size(0) == N && x.size(1) == C && x.size(2) == H &&
+                  x.size(3) == W,
+              "conv_dgrad2_x: x shape must match dx (N,C,H,W)");
+  TORCH_CHECK(dgrad2_ok(H, W, (int)C, K),
+              "conv_dgrad2_x: unsupported shape");
+  const void* accp = nullptr;
+  at::Tensor ac;
+  if (acc.has_value()) {
+    ac = acc->scalar_type() == at::kBFloat16
+             ? acc->contiguous(at::MemoryFormat::ChannelsLast)
+             : acc->to(at::kBFloat16)
+                   .contiguous(at::MemoryFormat::ChannelsLast);
+    TORCH_CHECK(ac.is_cuda() && ac.dim() == 4 && ac.size(0) == N &&
+                    ac.size(1) == C && ac.size(2) == H && ac.size(3) == W,
+                "conv_dgrad2_x: acc shape must match dx (N,C,H,W)");
+    accp = ac.data_ptr();
+  }
+  auto dx = at::empty({N, C, H, W}, g.options(),
+                      at::MemoryFormat::ChannelsLast);
+  int rc = bdbnn_conv_dgrad2_x(g.data_ptr(), wd.data_ptr(), x.data_ptr(),
+                               dx.data_ptr(), accp, (int)mode, (float)t,
+                               (float)k, N, H, W, (int)C, K, cur_stream());
+  TORCH_CHECK(rc == 0, "conv_dgrad2_x: launch rejected the shape");
+  return dx;
+}
+
 // ---------------- MFMA wgrad v2 (hot path) ----------------
 
 at::Tensor repack_cplane(const at::Tensor& xp, int64_t C, int64_t W) {
@@ -1002,6 +1054,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "clip-STE mask (3x3/s1/p1); optional acc adds a same-shape "
         "skip-gradient tensor in the epilogue",
         py::arg("g"), py::arg("wd"), py::arg("mp"), py::arg("C"),
+        py::arg("acc") = py::none());
+  m.def("conv_dgrad2_x", &conv_dgrad2_x,
+        "conv_dgrad2 with a value mask of the saved bf16 activation x in "
+        "the epilogue: mode 1 = ReAct polynomial, 2 = EDE(t, k)",
+        py::arg("g"), py::arg("wd"), py::arg("x"), py::arg("C"),
+        py::arg("mode"), py::arg("t"), py::arg("k"),
         py::arg("acc") = py::none());
   m.def("dgrad_weight_decode", &dgrad_weight_decode,
         "packed bits -> mirrored transposed +-alpha bf16 [9][C][K]");

@@ -10,7 +10,9 @@
 // backward by dgrad_weight_decode below), and mask is the clip-STE
 // bitplane packed by the forward (csrc/pack.hip) — applied in the
 // epilogue, so the old mask_mul_packed pass over the full dx tensor
-// disappears.
+// disappears.  The ReAct-polynomial and EDE activation modes use the
+// same kernel with a value mask of the saved bf16 activation instead of
+// the bitplane (MODE template parameter, conv_dgrad2_x).
 //
 // Why v2 is fast where v1 (csrc/conv_dgrad.hip) was 4-6x behind MIOpen:
 //   * HALO staging: the block's g tile is staged ONCE per 64-channel
@@ -61,11 +63,35 @@ struct Dgrad2Params {
 // ACC: fuse the residual-skip gradient (same-shape bf16 NHWC tensor)
 // into the epilogue store — dx = mask*acc + skip_grad — replacing the
 // separate autograd accumulation pass (one full read+write of dx).
-template <int WP, int RB, int GB, bool ACC>
+// MODE: which activation-gradient mask the epilogue applies
+//   0  clip-STE, one bit per element from the packed plane `mp`
+//   1  ReAct polynomial of x  (2+2x on [-1,0), 2-2x on [0,1), else 0)
+//   2  EDE  k*t*(1 - tanh^2(t*x))
+// Modes 1/2 depend on the VALUE of x, so they read the saved bf16 NHWC
+// activation `xin` at the very address they store dx to (`mp` unused);
+// semantics are those of ste_mask_mul_kernel (csrc/pack.hip).
+template <int MODE>
+__device__ __forceinline__ float dgrad2_value_mask(float x, float et,
+                                                   float ekt) {
+  static_assert(MODE == 1 || MODE == 2, "value mask: mode 1 or 2");
+  if constexpr (MODE == 1) {
+    return (x >= -1.f && x < 0.f) ? 2.f + 2.f * x
+         : (x >= 0.f && x < 1.f) ? 2.f - 2.f * x : 0.f;
+  }
+  // 1 - tanh^2(u) = 4e/(1+e)^2 with e = exp(-2|u|) in (0,1]: nothing
+  // can overflow, and large |t*x| underflows cleanly to 0 (the
+  // tanh-then-square form is fine too, but exp(+2u) variants are not)
+  float e = __expf(-2.f * fabsf(et * x));
+  float d = 1.f + e;
+  return ekt * __fdividef(4.f * e, d * d);
+}
+
+template <int WP, int RB, int GB, bool ACC, int MODE>
 __global__ __launch_bounds__(512, 2) void conv_dgrad2_kernel(
     const __bf16* __restrict__ g, const __bf16* __restrict__ wd,
     const uint32_t* __restrict__ mp, __bf16* __restrict__ dx,
-    const __bf16* __restrict__ accp,
+    const __bf16* __restrict__ accp, const __bf16* __restrict__ xin,
+    float et, float ek,
     Dgrad2Params p, int grid_m, int nb_m, int tiles_per_block) {
   constexpr int WH = WP + 2;                  // halo row width
   constexpr int NHE = GB * (RB + 2) * WH;     // halo entries (128 B each)
@@ -197,11 +223,13 @@ __global__ __launch_bounds__(512, 2) void conv_dgrad2_kernel(
 #define B_WRITE(buf)                                                      \
   *(uint4*)&blds[buf][b_c * DG2_BK + ((b_k8 ^ (b_c & 7)) << 3)] = breg;
 
-  // epilogue: clip-STE mask from the packed bitplane, bf16 store.
+  // epilogue: clip-STE mask from the packed bitplane (MODE 0) or value
+  // mask of the saved activation (MODE 1/2), bf16 store.
   // C/D layout: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
   const int ccol = c0 + wc + lrow;
   const int cw_word = ccol >> 5;
   const int cbit = ccol & 31;
+  const float ekt = ek * et;
 #define EPILOGUE(tb)                                                      \
   {                                                                       \
     _Pragma("unroll")                                                     \
@@ -210,6 +238,7 @@ __global__ __launch_bounds__(512, 2) void conv_dgrad2_kernel(
       const int mbase = wm0 + half * 32 + 4 * lk8;                        \
       int pixr[16];                                                       \
       uint32_t mpw[16];                                                   \
+      uint16_t xv[16];                                                    \
       uint16_t av[16];                                                    \
       _Pragma("unroll")                                                   \
       for (int reg = 0; reg < 16; ++reg)                                  \
@@ -221,15 +250,22 @@ __global__ __launch_bounds__(512, 2) void conv_dgrad2_kernel(
       _Pragma("unroll")                                                   \
       for (int reg = 0; reg < 16; ++reg) {                                \
         int64_t pz = pixr[reg] < 0 ? 0 : (int64_t)pixr[reg];              \
-        mpw[reg] = mp[pz * p.CW + cw_word];                               \
-        if (ACC) av[reg] = *(const uint16_t*)(accp + pz * p.C + ccol);    \
+        if constexpr (MODE == 0) mpw[reg] = mp[pz * p.CW + cw_word];      \
+        else xv[reg] = *(const uint16_t*)(xin + pz * p.C + ccol);         \
+        if constexpr (ACC)                                                \
+          av[reg] = *(const uint16_t*)(accp + pz * p.C + ccol);           \
       }                                                                   \
       _Pragma("unroll")                                                   \
       for (int reg = 0; reg < 16; ++reg) {                                \
         int pix = pixr[reg];                                              \
         if (pix < 0) continue;                                            \
-        float v = (mpw[reg] >> cbit) & 1 ? acc[reg] : 0.f;                \
-        if (ACC) v += bf16_to_f32(av[reg]);                               \
+        float v;                                                          \
+        if constexpr (MODE == 0)                                          \
+          v = (mpw[reg] >> cbit) & 1 ? acc[reg] : 0.f;                    \
+        else                                                              \
+          v = acc[reg] *                                                  \
+              dgrad2_value_mask<MODE>(bf16_to_f32(xv[reg]), et, ekt);     \
+        if constexpr (ACC) v += bf16_to_f32(av[reg]);                     \
         uint16_t h = f32_to_bf16(v);                                      \
         *(uint16_t*)(dx + (int64_t)pix * p.C + ccol) = h;                 \
       }                                                                   \
@@ -312,10 +348,11 @@ __global__ __launch_bounds__(512, 2) void conv_dgrad2_kernel(
 
 // ---------------- host launcher ----------------
 
-extern "C" int bdbnn_conv_dgrad2(const void* g, const void* wd,
-                                 const uint32_t* mp, void* dx,
-                                 const void* accp, int N, int H,
-                                 int W, int C, int K, hipStream_t stream) {
+template <int MODE>
+static int dgrad2_launch(const void* g, const void* wd, const uint32_t* mp,
+                         void* dx, const void* accp, const void* xin,
+                         float et, float ek, int N, int H, int W, int C,
+                         int K, hipStream_t stream) {
   if (C % 64 || K % 64 || W > 64) return -1;
   Dgrad2Params p;
   p.N = N; p.H = H; p.W = W; p.C = C; p.K = K;
@@ -334,13 +371,16 @@ extern "C" int bdbnn_conv_dgrad2(const void* g, const void* wd,
     nb_m = (grid_m + tpb - 1) / tpb;                                      \
     dim3 grid(nb_m * n_ctile);                                            \
     if (accp)                                                             \
-      conv_dgrad2_kernel<WPV, RBV, GBV, true><<<grid, 512, 0, stream>>>(  \
-          (const __bf16*)g, (const __bf16*)wd, mp, (__bf16*)dx,           \
-          (const __bf16*)accp, p, grid_m, nb_m, tpb);                     \
+      conv_dgrad2_kernel<WPV, RBV, GBV, true, MODE>                       \
+          <<<grid, 512, 0, stream>>>(                                     \
+              (const __bf16*)g, (const __bf16*)wd, mp, (__bf16*)dx,       \
+              (const __bf16*)accp, (const __bf16*)xin, et, ek, p, grid_m, \
+              nb_m, tpb);                                                 \
     else                                                                  \
-      conv_dgrad2_kernel<WPV, RBV, GBV, false><<<grid, 512, 0, stream>>>( \
-          (const __bf16*)g, (const __bf16*)wd, mp, (__bf16*)dx, nullptr,  \
-          p, grid_m, nb_m, tpb);                                          \
+      conv_dgrad2_kernel<WPV, RBV, GBV, false, MODE>                      \
+          <<<grid, 512, 0, stream>>>(                                     \
+              (const __bf16*)g, (const __bf16*)wd, mp, (__bf16*)dx,       \
+              nullptr, (const __bf16*)xin, et, ek, p, grid_m, nb_m, tpb); \
     return 0;                                                             \
   }
   if (W <= 8) {
@@ -354,6 +394,30 @@ extern "C" int bdbnn_conv_dgrad2(const void* g, const void* wd,
     LAUNCH(64, 4, 1);
   }
 #undef LAUNCH
+}
+
+extern "C" int bdbnn_conv_dgrad2(const void* g, const void* wd,
+                                 const uint32_t* mp, void* dx,
+                                 const void* accp, int N, int H,
+                                 int W, int C, int K, hipStream_t stream) {
+  return dgrad2_launch<0>(g, wd, mp, dx, accp, nullptr, 0.f, 0.f, N, H, W,
+                          C, K, stream);
+}
+
+// value-mask variant: x is the saved bf16 NHWC activation (same shape as
+// dx); mode 1 = ReAct polynomial, 2 = EDE(t, k)
+extern "C" int bdbnn_conv_dgrad2_x(const void* g, const void* wd,
+                                   const void* x, void* dx,
+                                   const void* accp, int mode, float t,
+                                   float k, int N, int H, int W, int C,
+                                   int K, hipStream_t stream) {
+  if (mode == 1)
+    return dgrad2_launch<1>(g, wd, nullptr, dx, accp, x, 0.f, 0.f, N, H, W,
+                            C, K, stream);
+  if (mode == 2)
+    return dgrad2_launch<2>(g, wd, nullptr, dx, accp, x, t, k, N, H, W, C,
+                            K, stream);
+  return -2;
 }
 
 // ---------------- mirrored/transposed weight decode ----------------

@@ -13,8 +13,10 @@ ref:utils/KD_loss.py:6-7,60):
 
 GPU path (CUDA tensors): bit-packed XNOR+popcount convolution via the
 in-tree HIP extension (csrc/xnor_conv.hip), activations packed on the fly
-(csrc/pack.hip), backward as dense MFMA-bf16 conv on the decoded +-1
-operands (MIOpen) with fused STE/EDE mask kernels.  Requires NHWC
+(csrc/pack.hip), backward as hand-written MFMA-bf16 dgrad/wgrad
+(csrc/conv_bwd.hip) with the clip-STE / ReAct / EDE mask fused into the
+dgrad epilogue on stride-1 3x3 bf16 convs; elsewhere dense conv on the
+decoded +-1 operands (MIOpen) with separate mask kernels.  Requires NHWC
 (channels_last) activations and C % 32 == 0 for the packed path; the
 engine puts models in channels_last.
 
@@ -70,6 +72,7 @@ class BinaryConvFunction(torch.autograd.Function):
         ctx.t = t
         ctx.k = k
         ctx.packed = False
+        ctx.valmask = False
         # deferred residual-skip gradient: the consuming BN's backward
         # (which runs first) stashes its dskip here instead of returning
         # it, and this conv's dgrad adds it in the epilogue — removing
@@ -101,9 +104,27 @@ class BinaryConvFunction(torch.autograd.Function):
                 ctx.in_channels = x.shape[1]
                 ctx.save_for_backward(w, xp, mp, wp, alpha)
             else:
-                xp = (xp_pre if xp_pre is not None else nat.sign_pack_nhwc(
-                    x.contiguous(memory_format=torch.channels_last)))
-                ctx.save_for_backward(x, w)
+                # value-mask modes (ReAct polynomial / EDE): the mask
+                # depends on the value of x, so the fp activation IS
+                # saved (channels_last, the copy made for packing) next
+                # to the tiny sign plane / packed weights that the owned
+                # MFMA backward consumes.  The kernel reads x at dx's
+                # NHWC address, so the saved copy is channels_last even
+                # when xp_pre spares the pack: free for the engine's
+                # channels_last tensors (contiguous() returns x itself),
+                # one layout copy per forward for an NCHW caller — the
+                # copy the fallback's decode/mask ops made in backward
+                x_cl = x.contiguous(memory_format=torch.channels_last)
+                xp = (xp_pre if xp_pre is not None
+                      else nat.sign_pack_nhwc(x_cl))
+                ctx.valmask = True
+                if t is not None and k is not None:
+                    ctx.mask_mode, ctx.mask_t, ctx.mask_k = (
+                        2, float(t), float(k))
+                else:
+                    ctx.mask_mode, ctx.mask_t, ctx.mask_k = (
+                        {"ste": 0, "approx": 1}[act_mode], 0.0, 0.0)
+                ctx.save_for_backward(w, xp, x_cl, wp, alpha)
             res = nat.xnor_conv_fwd(
                 xp, wp, alpha, stab, x.shape[1], stride, padding,
                 x.dtype == torch.bfloat16, want_stats)
@@ -167,7 +188,30 @@ class BinaryConvFunction(torch.autograd.Function):
             dw = nat.ste_mask_mul(dwb, w, 0, 0.0, 0.0)
             return (dx, dw.to(w.dtype), None, None, None, None, None,
                     None, None, None, None)
-        x, w = ctx.saved_tensors
+        if ctx.valmask:
+            w, xp, x, wp, alpha = ctx.saved_tensors
+            nat = _C.native_required()
+            C, K, kh = x.shape[1], w.shape[0], w.shape[2]
+            H, W = g.shape[2], g.shape[3]
+            # same hand-written MFMA kernels as the clip-STE path; the
+            # dgrad epilogue evaluates the ReAct / EDE mask from x
+            use2 = (_MFMA_BWD and ctx.mask_mode != 0
+                    and g.dtype == torch.bfloat16
+                    and x.dtype == torch.bfloat16
+                    and stride == 1 and padding == 1 and kh == 3
+                    and nat.dgrad2_supported(H, W, C, K))
+            if use2:
+                g = g.contiguous(memory_format=torch.channels_last)
+                wd = nat.dgrad_weight_decode(wp, alpha, C)
+                dx = nat.conv_dgrad2_x(g, wd, x, C, ctx.mask_mode,
+                                       ctx.mask_t, ctx.mask_k, acc)
+                xcp = nat.repack_cplane(xp, C, W)
+                dwT = nat.conv_wgrad2(g, xcp, C)
+                dw = nat.wgrad_finish(dwT, w.float())
+                return (dx, dw.to(w.dtype), None, None, None, None, None,
+                        None, None, None, None)
+        else:
+            x, w = ctx.saved_tensors
         if x.is_cuda:
             nat = _C.native_required()
             # decode +-1 operands in the compute dtype for the dense MFMA pass
