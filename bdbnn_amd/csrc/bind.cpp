@@ -64,6 +64,20 @@ void bdbnn_dgrad_wdec(const uint32_t*, const float*, void*, int, int,
 int bdbnn_conv_wgrad2(const void*, const uint64_t*, float*, int, int, int,
                       int, int, hipStream_t);
 int bdbnn_wgrad2_nslab(int, int, int, int, int);
+int bdbnn_dgrad2_s2_supported(int, int, int, int, int);
+int bdbnn_s2_kernels_can_run(int, int, int, int, int);
+int bdbnn_conv_dgrad2_s2(const void*, const void*, const uint32_t*,
+                         const void*, void*, const void*, int, int, float,
+                         float, int, int, int, int, int, hipStream_t);
+void bdbnn_dgrad_wdec_1x1(const uint32_t*, const float*, void*, int, int,
+                          hipStream_t);
+int bdbnn_wgrad2_s2_nslab(int, int, int, int, int, int);
+int bdbnn_conv_wgrad2_s2(const void*, const uint64_t*, float*, int, int,
+                         int, int, int, int, hipStream_t);
+void bdbnn_repack_cplane_s2(const uint32_t*, uint64_t*, int, int, int, int,
+                            hipStream_t);
+void bdbnn_wgrad_finish_s2(const float*, const float*, float*, int, int,
+                           int, int, hipStream_t);
 void bdbnn_stem_pack_x4(const void*, void*, int64_t, bool, hipStream_t);
 void bdbnn_stem_pack_w4(const float*, void*, hipStream_t);
 void bdbnn_stem_fwd(const void*, const void*, void*, int, int, int,
@@ -867,6 +881,198 @@ at::Tensor wgrad_finish(const at::Tensor& dwT, const at::Tensor& w) {
   return dw;
 }
 
+// ---------------- MFMA backward, stride 2 (csrc/conv_bwd_s2.hip) ---------
+
+// shape predicates of the stride-2 path; H, W are the INPUT (dx) size,
+// ks the kernel size (3 -> pad 1, 1 -> pad 0).  dgrad2_s2_ok: what the
+// kernels can run (argument check of the entry points);
+// dgrad2_s2_routed: the routing predicate exposed to python, which also
+// excludes the shapes measured slower than the fallback
+static bool s2_dims_sane(int64_t H, int64_t W, int64_t C, int64_t K) {
+  return H >= 1 && W >= 1 && H <= (1 << 20) && C <= (1 << 20) &&
+         K <= (1 << 20);
+}
+static bool dgrad2_s2_ok(int64_t H, int64_t W, int64_t C, int64_t K,
+                         int64_t ks) {
+  return s2_dims_sane(H, W, C, K) &&
+         bdbnn_s2_kernels_can_run((int)H, (int)W, (int)C, (int)K,
+                                  (int)ks) != 0;
+}
+static bool dgrad2_s2_routed(int64_t H, int64_t W, int64_t C, int64_t K,
+                             int64_t ks) {
+  return s2_dims_sane(H, W, C, K) &&
+         bdbnn_dgrad2_s2_supported((int)H, (int)W, (int)C, (int)K,
+                                   (int)ks) != 0;
+}
+
+at::Tensor dgrad_weight_decode_1x1(const at::Tensor& wp,
+                                   const at::Tensor& alpha, int64_t C) {
+  TORCH_CHECK(wp.is_cuda() && wp.dim() == 4 && wp.size(1) == 1 &&
+                  wp.size(2) == 1 && wp.scalar_type() == at::kInt,
+              "dgrad_weight_decode_1x1: wp must be packed 1x1 weights "
+              "[K][1][1][CW] int32");
+  int K = (int)wp.size(0);
+  TORCH_CHECK(K % 8 == 0 && C % 32 == 0 && wp.size(3) == C / 32,
+              "dgrad_weight_decode_1x1: C must match wp (K%8, C%32)");
+  TORCH_CHECK(alpha.is_cuda() && alpha.scalar_type() == at::kFloat &&
+                  alpha.numel() == K,
+              "dgrad_weight_decode_1x1: alpha must be fp32 [K]");
+  auto wd = at::empty({1, C, K}, wp.options().dtype(at::kBFloat16));
+  auto al = alpha.contiguous();
+  auto wpc = wp.contiguous();
+  bdbnn_dgrad_wdec_1x1((const uint32_t*)wpc.data_ptr<int>(),
+                       al.data_ptr<float>(), wd.data_ptr(), (int)C, K,
+                       cur_stream());
+  return wd;
+}
+
+// dx of a 3x3/s2/p1 (wd [9][C][K]) or 1x1/s2/p0 (wd [1][C][K]) conv at
+// input size (H, W); mode 0 masks with the bitplane mp, modes 1/2 with
+// the value mask of the saved activation x
+at::Tensor conv_dgrad2_s2(const at::Tensor& g, const at::Tensor& wd,
+                          int64_t H, int64_t W, int64_t C, int64_t mode,
+                          const c10::optional<at::Tensor>& mp,
+                          const c10::optional<at::Tensor>& x, double t,
+                          double k, const c10::optional<at::Tensor>& acc) {
+  TORCH_CHECK(g.is_cuda() && g.dim() == 4 &&
+                  g.scalar_type() == at::kBFloat16,
+              "conv_dgrad2_s2: g must be a 4-D bf16 CUDA tensor");
+  TORCH_CHECK(g.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "conv_dgrad2_s2: g must be channels_last");
+  int N = (int)g.size(0), K = (int)g.size(1);
+  TORCH_CHECK(wd.is_cuda() && wd.dim() == 3 &&
+                  wd.scalar_type() == at::kBFloat16 && wd.is_contiguous(),
+              "conv_dgrad2_s2: wd must be contiguous bf16 [ks*ks][C][K]");
+  TORCH_CHECK(wd.size(0) == 9 || wd.size(0) == 1,
+              "conv_dgrad2_s2: wd.size(0) must be 9 (3x3) or 1 (1x1)");
+  int ks = wd.size(0) == 9 ? 3 : 1;
+  TORCH_CHECK(wd.size(1) == C && wd.size(2) == K,
+              "conv_dgrad2_s2: wd must be [ks*ks][C][K] for this g and C");
+  TORCH_CHECK(dgrad2_s2_ok(H, W, C, K, ks),
+              "conv_dgrad2_s2: unsupported shape (H, W, C, K, ks)");
+  int64_t Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  TORCH_CHECK(g.size(2) == Ho && g.size(3) == Wo,
+              "conv_dgrad2_s2: g spatial size must be the (Ho, Wo) implied "
+              "by (H, W, ks)");
+  TORCH_CHECK(mode >= 0 && mode <= 2,
+              "conv_dgrad2_s2: mode must be 0 (clip-STE), 1 (approx) or 2 "
+              "(EDE)");
+  const uint32_t* mp_ptr = nullptr;
+  const void* x_ptr = nullptr;
+  at::Tensor mpc;
+  if (mode == 0) {
+    TORCH_CHECK(mp.has_value() && !x.has_value(),
+                "conv_dgrad2_s2: mode 0 needs mp and x=None");
+    TORCH_CHECK(mp->is_cuda() && mp->scalar_type() == at::kInt &&
+                    mp->is_contiguous() && mp->size(-1) == C / 32 &&
+                    mp->numel() == (int64_t)N * H * W * (C / 32),
+                "conv_dgrad2_s2: mp must be the int32 mask bitplane "
+                "[N,H,W,C/32] at input resolution");
+    mp_ptr = (const uint32_t*)mp->data_ptr<int>();
+  } else {
+    TORCH_CHECK(x.has_value() && !mp.has_value(),
+                "conv_dgrad2_s2: modes 1/2 need x and mp=None");
+    TORCH_CHECK(x->is_cuda() && x->dim() == 4 &&
+                    x->scalar_type() == at::kBFloat16,
+                "conv_dgrad2_s2: x must be a 4-D bf16 CUDA tensor");
+    TORCH_CHECK(x->is_contiguous(at::MemoryFormat::ChannelsLast),
+                "conv_dgrad2_s2: x must be channels_last");
+    TORCH_CHECK(x->size(0) == N && x->size(1) == C && x->size(2) == H &&
+                    x->size(3) == W,
+                "conv_dgrad2_s2: x shape must match dx (N,C,H,W)");
+    x_ptr = x->data_ptr();
+  }
+  const void* accp = nullptr;
+  at::Tensor ac;
+  if (acc.has_value()) {
+    ac = acc->scalar_type() == at::kBFloat16
+             ? acc->contiguous(at::MemoryFormat::ChannelsLast)
+             : acc->to(at::kBFloat16)
+                   .contiguous(at::MemoryFormat::ChannelsLast);
+    TORCH_CHECK(ac.is_cuda() && ac.dim() == 4 && ac.size(0) == N &&
+                    ac.size(1) == C && ac.size(2) == H && ac.size(3) == W,
+                "conv_dgrad2_s2: acc shape must match dx (N,C,H,W)");
+    accp = ac.data_ptr();
+  }
+  auto dx = at::empty({N, C, H, W}, g.options(),
+                      at::MemoryFormat::ChannelsLast);
+  int rc = bdbnn_conv_dgrad2_s2(g.data_ptr(), wd.data_ptr(), mp_ptr, x_ptr,
+                                dx.data_ptr(), accp, ks, (int)mode,
+                                (float)t, (float)k, N, (int)H, (int)W,
+                                (int)C, K, cur_stream());
+  TORCH_CHECK(rc == 0, "conv_dgrad2_s2: launch rejected the shape");
+  return dx;
+}
+
+at::Tensor repack_cplane_s2(const at::Tensor& xp, int64_t C, int64_t H,
+                            int64_t W) {
+  TORCH_CHECK(xp.is_cuda() && xp.dim() == 4 &&
+                  xp.scalar_type() == at::kInt && xp.is_contiguous(),
+              "repack_cplane_s2: xp must be contiguous int32 [N][H][W][CW]");
+  TORCH_CHECK(xp.size(3) == (C + 31) / 32,
+              "repack_cplane_s2: C does not match xp's word count");
+  TORCH_CHECK(xp.size(1) == H && xp.size(2) == W,
+              "repack_cplane_s2: H, W do not match xp");
+  TORCH_CHECK(W >= 1 && W <= 64, "repack_cplane_s2: W must be <= 64");
+  int NH = (int)(xp.size(0) * xp.size(1));
+  auto planes = at::empty({C, NH}, xp.options().dtype(at::kLong));
+  bdbnn_repack_cplane_s2((const uint32_t*)xp.data_ptr<int>(),
+                         (uint64_t*)planes.data_ptr<int64_t>(), NH, (int)W,
+                         (int)C, (int)xp.size(3), cur_stream());
+  return planes;
+}
+
+at::Tensor conv_wgrad2_s2(const at::Tensor& g, const at::Tensor& planes,
+                          int64_t C, int64_t H, int64_t W, int64_t ks) {
+  TORCH_CHECK(g.is_cuda() && g.dim() == 4 &&
+                  g.scalar_type() == at::kBFloat16,
+              "conv_wgrad2_s2: g must be a 4-D bf16 CUDA tensor");
+  TORCH_CHECK(g.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "conv_wgrad2_s2: g must be channels_last");
+  int N = (int)g.size(0), K = (int)g.size(1);
+  TORCH_CHECK(dgrad2_s2_ok(H, W, C, K, ks),
+              "conv_wgrad2_s2: unsupported shape (H, W, C, K, ks)");
+  TORCH_CHECK(g.size(2) == (H + 1) / 2 && g.size(3) == (W + 1) / 2,
+              "conv_wgrad2_s2: g spatial size must be the (Ho, Wo) implied "
+              "by (H, W, ks)");
+  TORCH_CHECK(planes.is_cuda() && planes.dim() == 2 &&
+                  planes.scalar_type() == at::kLong &&
+                  planes.is_contiguous() && planes.size(0) == C &&
+                  planes.size(1) == (int64_t)N * H,
+              "conv_wgrad2_s2: planes must be int64 [C][N*H] "
+              "(repack_cplane_s2)");
+  int nslab = bdbnn_wgrad2_s2_nslab(N, (int)H, (int)W, (int)C, K, (int)ks);
+  TORCH_CHECK(nslab > 0, "conv_wgrad2_s2: unsupported shape");
+  // per-m-split-block partial slabs; every word is written (no memset)
+  auto dwT = at::empty({nslab, ks * ks, C, K},
+                       g.options().dtype(at::kFloat));
+  int rc = bdbnn_conv_wgrad2_s2(g.data_ptr(),
+                                (const uint64_t*)planes.data_ptr<int64_t>(),
+                                dwT.data_ptr<float>(), (int)ks, N, (int)H,
+                                (int)W, (int)C, K, cur_stream());
+  TORCH_CHECK(rc == 0, "conv_wgrad2_s2: launch rejected the shape");
+  return dwT;
+}
+
+at::Tensor wgrad_finish_s2(const at::Tensor& dwT, const at::Tensor& w) {
+  TORCH_CHECK(w.is_cuda() && w.dim() == 4 && w.size(2) == w.size(3) &&
+                  (w.size(2) == 3 || w.size(2) == 1) &&
+                  w.scalar_type() == at::kFloat,
+              "wgrad_finish_s2: w must be fp32 [K][C][ks][ks], ks in {1,3}");
+  int K = (int)w.size(0), C = (int)w.size(1);
+  int T = (int)(w.size(2) * w.size(3));
+  TORCH_CHECK(dwT.is_cuda() && dwT.dim() == 4 && dwT.size(1) == T &&
+                  dwT.size(2) == C && dwT.size(3) == K &&
+                  dwT.scalar_type() == at::kFloat,
+              "wgrad_finish_s2: dwT must be fp32 [nslab][ks*ks][C][K]");
+  auto wc = w.contiguous();
+  auto dw = at::empty_like(wc);
+  bdbnn_wgrad_finish_s2(dwT.contiguous().data_ptr<float>(),
+                        wc.data_ptr<float>(), dw.data_ptr<float>(), C, K, T,
+                        (int)dwT.size(0), cur_stream());
+  return dw;
+}
+
 // ---------------- experimental MFMA dgrad (v1, kept for A/B) -------------
 
 at::Tensor conv_dgrad(const at::Tensor& g, const at::Tensor& wp,
@@ -1075,6 +1281,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "activation sign bits -> padded per-channel u64 row planes");
   m.def("wgrad_finish", &wgrad_finish,
         "dwT transpose to [K][C][3][3] + |w|<=1 STE mask, one pass");
+  m.def("dgrad2_s2_supported",
+        [](int64_t H, int64_t W, int64_t C, int64_t K, int64_t ks) {
+          return dgrad2_s2_routed(H, W, C, K, ks);
+        },
+        "routing predicate of the stride-2 MFMA backward; H, W are the "
+        "input (dx) size, ks in {3 (pad 1), 1 (pad 0)}; false also for "
+        "the shapes the kernels run but lose on (3x3 with C >= 128 and "
+        "K >= 256)",
+        py::arg("H"), py::arg("W"), py::arg("C"), py::arg("K"),
+        py::arg("ks"));
+  m.def("conv_dgrad2_s2", &conv_dgrad2_s2,
+        "MFMA bf16 dgrad of a 3x3/s2/p1 (wd [9][C][K]) or 1x1/s2/p0 (wd "
+        "[1][C][K]) binary conv by pixel parity; mode 0 masks with the "
+        "bitplane mp, modes 1/2 with the value mask of x; optional acc "
+        "adds a same-shape skip-gradient tensor in the epilogue",
+        py::arg("g"), py::arg("wd"), py::arg("H"), py::arg("W"),
+        py::arg("C"), py::arg("mode"), py::arg("mp"), py::arg("x"),
+        py::arg("t"), py::arg("k"), py::arg("acc") = py::none());
+  m.def("dgrad_weight_decode_1x1", &dgrad_weight_decode_1x1,
+        "packed 1x1 bits -> transposed +-alpha bf16 [1][C][K]");
+  m.def("repack_cplane_s2", &repack_cplane_s2,
+        "activation sign bits -> per-channel u64 row planes split by "
+        "column parity (even columns low word, odd columns high word)",
+        py::arg("xp"), py::arg("C"), py::arg("H"), py::arg("W"));
+  m.def("conv_wgrad2_s2", &conv_wgrad2_s2,
+        "MFMA bf16 wgrad of a 3x3/s2/p1 or 1x1/s2/p0 binary conv from the "
+        "parity planes -> fp32 [nslab][ks*ks][C][K]",
+        py::arg("g"), py::arg("planes"), py::arg("C"), py::arg("H"),
+        py::arg("W"), py::arg("ks"));
+  m.def("wgrad_finish_s2", &wgrad_finish_s2,
+        "dwT slab sum + transpose to [K][C][ks][ks] + |w|<=1 STE mask");
   m.def("conv_dgrad", &conv_dgrad,
         "EXPERIMENTAL MFMA bf16 dgrad (3x3/s1/p1, packed weights)");
   m.def("conv_wgrad", &conv_wgrad,

@@ -33,10 +33,7 @@
 // Constraints (python falls back to the aten/MIOpen path otherwise):
 //   KH = KW = 3, stride = 1, pad = 1, C % 64 == 0, K % 64 == 0,
 //   W <= 64 (and H <= 8 when W <= 8), g bf16 NHWC, dx bf16 NHWC.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+#include "conv_bwd_common.h"
 
 #define DG2_BM 256       // M rows (padded pixels) per block
 #define DG2_BN 64        // dx channels per block
@@ -63,29 +60,9 @@ struct Dgrad2Params {
 // ACC: fuse the residual-skip gradient (same-shape bf16 NHWC tensor)
 // into the epilogue store — dx = mask*acc + skip_grad — replacing the
 // separate autograd accumulation pass (one full read+write of dx).
-// MODE: which activation-gradient mask the epilogue applies
-//   0  clip-STE, one bit per element from the packed plane `mp`
-//   1  ReAct polynomial of x  (2+2x on [-1,0), 2-2x on [0,1), else 0)
-//   2  EDE  k*t*(1 - tanh^2(t*x))
-// Modes 1/2 depend on the VALUE of x, so they read the saved bf16 NHWC
-// activation `xin` at the very address they store dx to (`mp` unused);
-// semantics are those of ste_mask_mul_kernel (csrc/pack.hip).
-template <int MODE>
-__device__ __forceinline__ float dgrad2_value_mask(float x, float et,
-                                                   float ekt) {
-  static_assert(MODE == 1 || MODE == 2, "value mask: mode 1 or 2");
-  if constexpr (MODE == 1) {
-    return (x >= -1.f && x < 0.f) ? 2.f + 2.f * x
-         : (x >= 0.f && x < 1.f) ? 2.f - 2.f * x : 0.f;
-  }
-  // 1 - tanh^2(u) = 4e/(1+e)^2 with e = exp(-2|u|) in (0,1]: nothing
-  // can overflow, and large |t*x| underflows cleanly to 0 (the
-  // tanh-then-square form is fine too, but exp(+2u) variants are not)
-  float e = __expf(-2.f * fabsf(et * x));
-  float d = 1.f + e;
-  return ekt * __fdividef(4.f * e, d * d);
-}
-
+// MODE: which activation-gradient mask the epilogue applies (0 clip-STE
+// bitplane, 1 ReAct polynomial, 2 EDE — dgrad2_value_mask,
+// conv_bwd_common.h)
 template <int WP, int RB, int GB, bool ACC, int MODE>
 __global__ __launch_bounds__(512, 2) void conv_dgrad2_kernel(
     const __bf16* __restrict__ g, const __bf16* __restrict__ wd,

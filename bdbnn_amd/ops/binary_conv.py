@@ -37,6 +37,10 @@ _CONV_STATS = os.environ.get("BDBNN_CONV_STATS", "0") == "1"
 # hand-written MFMA backward kernels (default ON; BDBNN_MFMA_BWD=0 falls
 # back to MIOpen igemm on decoded operands for A/B comparison)
 _MFMA_BWD = os.environ.get("BDBNN_MFMA_BWD", "1") != "0"
+# the stride-2 kernels of that backward (3x3/s2/p1 and 1x1/s2/p0,
+# csrc/conv_bwd_s2.hip) alone: BDBNN_MFMA_BWD_S2=0 sends just those convs
+# back to the MIOpen path while stride 1 stays on the owned kernels
+_MFMA_BWD_S2 = os.environ.get("BDBNN_MFMA_BWD_S2", "1") != "0"
 
 
 def _act_grad_mask(x: torch.Tensor, mode: str, t, k) -> torch.Tensor:
@@ -52,6 +56,31 @@ def _act_grad_mask(x: torch.Tensor, mode: str, t, k) -> torch.Tensor:
         g = torch.where(pos, 2.0 - 2.0 * x, g)
         return g
     return (x.abs() <= 1).to(x.dtype)
+
+
+def _use_s2(nat, g, x_dtype, w, stride, padding, H, W, C):
+    """Route a stride-2 conv's backward to the owned parity kernels?
+    (H, W) is the INPUT size; the native predicate decides the shape."""
+    K, kh, kw = w.shape[0], w.shape[2], w.shape[3]
+    return (_MFMA_BWD and _MFMA_BWD_S2 and g.dtype == torch.bfloat16
+            and x_dtype == torch.bfloat16 and stride == 2 and kh == kw
+            and (kh, padding) in ((3, 1), (1, 0))
+            and nat.dgrad2_s2_supported(H, W, C, K, kh))
+
+
+def _s2_backward(nat, g, w, xp, wp, alpha, C, H, W, mode, mp, x, t, k, acc):
+    """Owned stride-2 backward: parity-phase dgrad with the mask (and the
+    deferred skip grad, if any) in its epilogue, wgrad from the sign bits
+    repacked by column parity — no decoded activation, no mask pass."""
+    kh = w.shape[2]
+    g = g.contiguous(memory_format=torch.channels_last)
+    wd = (nat.dgrad_weight_decode(wp, alpha, C) if kh == 3
+          else nat.dgrad_weight_decode_1x1(wp, alpha, C))
+    dx = nat.conv_dgrad2_s2(g, wd, H, W, C, mode, mp, x, t, k, acc)
+    planes = nat.repack_cplane_s2(xp, C, H, W)
+    dwT = nat.conv_wgrad2_s2(g, planes, C, H, W, kh)
+    dw = nat.wgrad_finish_s2(dwT, w.float())
+    return dx, dw
 
 
 class BinaryConvFunction(torch.autograd.Function):
@@ -175,6 +204,13 @@ class BinaryConvFunction(torch.autograd.Function):
                 dw = nat.wgrad_finish(dwT, w.float())
                 return (dx, dw.to(w.dtype), None, None, None, None, None,
                         None, None, None, None)
+            if _use_s2(nat, g, ctx.x_dtype, w, stride, padding,
+                       xp.shape[1], xp.shape[2], C):
+                dx, dw = _s2_backward(nat, g, w, xp, wp, alpha, C,
+                                      xp.shape[1], xp.shape[2], 0, mp, None,
+                                      0.0, 0.0, acc)
+                return (dx, dw.to(w.dtype), None, None, None, None, None,
+                        None, None, None, None)
             xb = nat.decode_packed(xp, C, bf16)
             wb = nat.weight_decode(wp, alpha, C, bf16)
             dxb, dwb = torch.ops.aten.convolution_backward(
@@ -208,6 +244,14 @@ class BinaryConvFunction(torch.autograd.Function):
                 xcp = nat.repack_cplane(xp, C, W)
                 dwT = nat.conv_wgrad2(g, xcp, C)
                 dw = nat.wgrad_finish(dwT, w.float())
+                return (dx, dw.to(w.dtype), None, None, None, None, None,
+                        None, None, None, None)
+            if ctx.mask_mode != 0 and _use_s2(
+                    nat, g, x.dtype, w, stride, padding, x.shape[2],
+                    x.shape[3], C):
+                dx, dw = _s2_backward(nat, g, w, xp, wp, alpha, C,
+                                      x.shape[2], x.shape[3], ctx.mask_mode,
+                                      None, x, ctx.mask_t, ctx.mask_k, acc)
                 return (dx, dw.to(w.dtype), None, None, None, None, None,
                         None, None, None, None)
         else:

@@ -27,6 +27,7 @@ sources = [os.path.join(CSRC, f) for f in (
     "loss.hip",
     "conv_dgrad.hip",
     "conv_bwd.hip",
+    "conv_bwd_s2.hip",
     "conv_wgrad.hip",
     "stem_conv.hip",
     "xnor_conv.hip",
