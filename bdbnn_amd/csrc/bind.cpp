@@ -54,12 +54,11 @@ void bdbnn_ce_bwd(const void*, const int64_t*, const float*, void*, float,
                   int, int, bool, hipStream_t);
 void bdbnn_conv_dgrad(const void*, const uint32_t*, const float*, void*,
                       int, int, int, int, int, int, hipStream_t);
-int bdbnn_conv_dgrad2(const void*, const void*, const uint32_t*, void*,
-                      const void*, int, int, int, int, int, hipStream_t);
-int bdbnn_conv_dgrad2_x(const void*, const void*, const void*, void*,
-                        const void*, int, float, float, int, int, int, int,
-                        int, hipStream_t);
-void bdbnn_dgrad_wdec(const uint32_t*, const float*, void*, int, int,
+int bdbnn_conv_dgrad2(const void*, const void*, const uint32_t*,
+                      const void*, void*, const void*, int, float, float,
+                      int, int, int, int, int, hipStream_t);
+int bdbnn_dgrad2_supported(int, int, int, int);
+void bdbnn_dgrad_wdec(const uint32_t*, const float*, void*, int, int, int,
                       hipStream_t);
 int bdbnn_conv_wgrad2(const void*, const uint64_t*, float*, int, int, int,
                       int, int, hipStream_t);
@@ -69,15 +68,9 @@ int bdbnn_s2_kernels_can_run(int, int, int, int, int);
 int bdbnn_conv_dgrad2_s2(const void*, const void*, const uint32_t*,
                          const void*, void*, const void*, int, int, float,
                          float, int, int, int, int, int, hipStream_t);
-void bdbnn_dgrad_wdec_1x1(const uint32_t*, const float*, void*, int, int,
-                          hipStream_t);
 int bdbnn_wgrad2_s2_nslab(int, int, int, int, int, int);
 int bdbnn_conv_wgrad2_s2(const void*, const uint64_t*, float*, int, int,
                          int, int, int, int, hipStream_t);
-void bdbnn_repack_cplane_s2(const uint32_t*, uint64_t*, int, int, int, int,
-                            hipStream_t);
-void bdbnn_wgrad_finish_s2(const float*, const float*, float*, int, int,
-                           int, int, hipStream_t);
 void bdbnn_stem_pack_x4(const void*, void*, int64_t, bool, hipStream_t);
 void bdbnn_stem_pack_w4(const float*, void*, hipStream_t);
 void bdbnn_stem_fwd(const void*, const void*, void*, int, int, int,
@@ -87,9 +80,9 @@ void bdbnn_stem_wrw(const void*, const void*, float*, int, int, int,
                     hipStream_t);
 void bdbnn_stem_fold_dw4(const float*, float*, int, hipStream_t);
 void bdbnn_repack_cplane(const uint32_t*, uint64_t*, int, int, int, int,
-                         hipStream_t);
+                         bool, hipStream_t);
 void bdbnn_wgrad_finish(const float*, const float*, float*, int, int, int,
-                        hipStream_t);
+                        int, hipStream_t);
 void bdbnn_conv_wgrad(const void*, const uint32_t*, float*, int, int, int,
                       int, int, int, hipStream_t);
 void bdbnn_prelu_fwd(const void*, const float*, void*, int64_t, int, bool,
@@ -713,139 +706,207 @@ at::Tensor bn_act_eval(const at::Tensor& x,
   return out;
 }
 
-// ---------------- MFMA dgrad v2 (hot path) ----------------
+// ---------------- MFMA backward (csrc/conv_bwd.hip, conv_bwd_s2.hip) -----
+// Argument handling shared by the stride-1 and stride-2 entry points;
+// `who` is the python-visible name, for the message.
 
-at::Tensor dgrad_weight_decode(const at::Tensor& wp, const at::Tensor& alpha,
-                               int64_t C) {
-  TORCH_CHECK(wp.is_cuda() && wp.dim() == 4 && wp.size(1) == 3 &&
-                  wp.size(2) == 3,
-              "dgrad_weight_decode: packed 3x3 weights [K][3][3][CW]");
+static void check_grad_bf16_cl(const at::Tensor& g, const char* who) {
+  TORCH_CHECK(g.is_cuda() && g.dim() == 4 &&
+                  g.scalar_type() == at::kBFloat16,
+              who, ": g must be a 4-D bf16 CUDA tensor");
+  TORCH_CHECK(g.is_contiguous(at::MemoryFormat::ChannelsLast), who,
+              ": g must be channels_last");
+}
+
+// the saved activation of the value-mask modes, read at dx's address
+static void check_act_bf16_cl(const at::Tensor& x, int64_t N, int64_t C,
+                              int64_t H, int64_t W, const char* who) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
+                  x.scalar_type() == at::kBFloat16,
+              who, ": x must be a 4-D bf16 CUDA tensor");
+  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast), who,
+              ": x must be channels_last");
+  TORCH_CHECK(x.size(0) == N && x.size(1) == C && x.size(2) == H &&
+                  x.size(3) == W,
+              who, ": x shape must match dx (N,C,H,W)");
+}
+
+// the deferred skip gradient as the kernels read it (bf16 channels_last,
+// dx's shape); undefined when there is none.  The caller holds the
+// returned tensor until its launch is queued.
+static at::Tensor acc_as_bf16_cl(const c10::optional<at::Tensor>& acc,
+                                 int64_t N, int64_t C, int64_t H, int64_t W,
+                                 const char* who) {
+  if (!acc.has_value()) return at::Tensor();
+  at::Tensor ac =
+      acc->scalar_type() == at::kBFloat16
+          ? acc->contiguous(at::MemoryFormat::ChannelsLast)
+          : acc->to(at::kBFloat16).contiguous(at::MemoryFormat::ChannelsLast);
+  TORCH_CHECK(ac.is_cuda() && ac.dim() == 4 && ac.size(0) == N &&
+                  ac.size(1) == C && ac.size(2) == H && ac.size(3) == W,
+              who, ": acc shape must match dx (N,C,H,W)");
+  return ac;
+}
+
+static at::Tensor empty_dx(const at::Tensor& g, int64_t N, int64_t C,
+                           int64_t H, int64_t W) {
+  return at::empty({N, C, H, W}, g.options(),
+                   at::MemoryFormat::ChannelsLast);
+}
+
+// packed bits -> mirrored transposed +-alpha bf16 [ks*ks][C][K]
+static at::Tensor dgrad_wdec_impl(const at::Tensor& wp,
+                                  const at::Tensor& alpha, int64_t C,
+                                  int64_t ks, const char* who) {
+  TORCH_CHECK(wp.is_cuda() && wp.dim() == 4 && wp.size(1) == ks &&
+                  wp.size(2) == ks && wp.scalar_type() == at::kInt,
+              who, ": wp must be packed ", ks, "x", ks,
+              " weights [K][ks][ks][CW] int32");
   int K = (int)wp.size(0);
-  TORCH_CHECK(K % 8 == 0 && C % 32 == 0, "dgrad_weight_decode: K%8, C%32");
-  auto wd = at::empty({9, C, K}, wp.options().dtype(at::kBFloat16));
+  TORCH_CHECK(K % 8 == 0 && C % 32 == 0 && wp.size(3) == C / 32, who,
+              ": C must match wp (K%8, C%32)");
+  TORCH_CHECK(alpha.is_cuda() && alpha.scalar_type() == at::kFloat &&
+                  alpha.numel() == K,
+              who, ": alpha must be fp32 [K]");
+  auto wd = at::empty({ks * ks, C, K}, wp.options().dtype(at::kBFloat16));
   auto al = alpha.contiguous();
   auto wpc = wp.contiguous();
   bdbnn_dgrad_wdec((const uint32_t*)wpc.data_ptr<int>(),
                    al.data_ptr<float>(), wd.data_ptr(), (int)C, K,
-                   cur_stream());
+                   (int)(ks * ks), cur_stream());
   return wd;
 }
 
-// supported(N,H,W,C,K) mirror of the kernel's launch table
-static bool dgrad2_ok(int H, int W, int C, int K) {
-  if (C % 64 || K % 64 || W > 64) return false;
-  if (W <= 8 && H > 8) return false;
-  return true;
+at::Tensor dgrad_weight_decode(const at::Tensor& wp, const at::Tensor& alpha,
+                               int64_t C) {
+  return dgrad_wdec_impl(wp, alpha, C, 3, "dgrad_weight_decode");
+}
+
+at::Tensor dgrad_weight_decode_1x1(const at::Tensor& wp,
+                                   const at::Tensor& alpha, int64_t C) {
+  return dgrad_wdec_impl(wp, alpha, C, 1, "dgrad_weight_decode_1x1");
+}
+
+// activation sign bits -> per-channel u64 row planes [C][N*H]; parity:
+// columns split even (low word) / odd (high word) for the stride-2 wgrad
+static at::Tensor repack_cplane_impl(const at::Tensor& xp, int64_t C,
+                                     c10::optional<int64_t> H, int64_t W,
+                                     bool parity, const char* who) {
+  TORCH_CHECK(xp.is_cuda() && xp.dim() == 4 &&
+                  xp.scalar_type() == at::kInt && xp.is_contiguous(),
+              who, ": xp must be contiguous int32 [N][H][W][CW]");
+  TORCH_CHECK(xp.size(3) == (C + 31) / 32, who,
+              ": C does not match xp's word count");
+  TORCH_CHECK((!H.has_value() || xp.size(1) == *H) && xp.size(2) == W, who,
+              ": H, W do not match xp");
+  TORCH_CHECK(W >= 1 && W <= 64, who, ": W must be <= 64");
+  int NH = (int)(xp.size(0) * xp.size(1));
+  auto planes = at::empty({C, NH}, xp.options().dtype(at::kLong));
+  bdbnn_repack_cplane((const uint32_t*)xp.data_ptr<int>(),
+                      (uint64_t*)planes.data_ptr<int64_t>(), NH, (int)W,
+                      (int)C, (int)xp.size(3), parity, cur_stream());
+  return planes;
+}
+
+at::Tensor repack_cplane(const at::Tensor& xp, int64_t C, int64_t W) {
+  return repack_cplane_impl(xp, C, c10::nullopt, W, false, "repack_cplane");
+}
+
+at::Tensor repack_cplane_s2(const at::Tensor& xp, int64_t C, int64_t H,
+                            int64_t W) {
+  return repack_cplane_impl(xp, C, H, W, true, "repack_cplane_s2");
+}
+
+// dw[K][C][ks][ks] = sum of the wgrad slabs, transposed, |w|<=1 STE mask
+static at::Tensor wgrad_finish_impl(const at::Tensor& dwT,
+                                    const at::Tensor& w, bool allow_1x1,
+                                    const char* who) {
+  TORCH_CHECK(w.is_cuda() && w.dim() == 4 && w.size(2) == w.size(3) &&
+                  (w.size(2) == 3 || (allow_1x1 && w.size(2) == 1)) &&
+                  w.scalar_type() == at::kFloat,
+              who, ": w must be fp32 [K][C][ks][ks], ks ",
+              allow_1x1 ? "in {1,3}" : "= 3");
+  int K = (int)w.size(0), C = (int)w.size(1);
+  int T = (int)(w.size(2) * w.size(3));
+  TORCH_CHECK(dwT.is_cuda() && dwT.dim() == 4 && dwT.size(1) == T &&
+                  dwT.size(2) == C && dwT.size(3) == K &&
+                  dwT.scalar_type() == at::kFloat,
+              who, ": dwT must be fp32 [nslab][ks*ks][C][K]");
+  auto wc = w.contiguous();
+  auto dw = at::empty_like(wc);
+  bdbnn_wgrad_finish(dwT.contiguous().data_ptr<float>(),
+                     wc.data_ptr<float>(), dw.data_ptr<float>(), C, K, T,
+                     (int)dwT.size(0), cur_stream());
+  return dw;
+}
+
+at::Tensor wgrad_finish(const at::Tensor& dwT, const at::Tensor& w) {
+  return wgrad_finish_impl(dwT, w, false, "wgrad_finish");
+}
+
+at::Tensor wgrad_finish_s2(const at::Tensor& dwT, const at::Tensor& w) {
+  return wgrad_finish_impl(dwT, w, true, "wgrad_finish_s2");
+}
+
+// ---------------- stride 1 (3x3/s1/p1) ----------------
+
+// dx with the mask in the epilogue: mode 0 reads the clip-STE bitplane
+// mp, modes 1 (ReAct polynomial) / 2 (EDE) evaluate the value mask of
+// the saved bf16 activation x
+static at::Tensor conv_dgrad2_impl(const at::Tensor& g, const at::Tensor& wd,
+                                   const at::Tensor* mp, const at::Tensor* x,
+                                   int64_t C, int64_t mode, double t,
+                                   double k,
+                                   const c10::optional<at::Tensor>& acc,
+                                   const char* who) {
+  check_grad_bf16_cl(g, who);
+  int N = (int)g.size(0), K = (int)g.size(1);
+  int H = (int)g.size(2), W = (int)g.size(3);
+  TORCH_CHECK(wd.is_cuda() && wd.dim() == 3 && wd.size(0) == 9 &&
+                  wd.size(1) == C && wd.size(2) == K &&
+                  wd.scalar_type() == at::kBFloat16 && wd.is_contiguous(),
+              who, ": decoded weights [9][C][K] bf16");
+  if (mp) {
+    TORCH_CHECK(mp->size(-1) == C / 32 &&
+                    mp->numel() == (int64_t)N * H * W * (C / 32),
+                who, ": mask bitplane [...P...][C/32]");
+  } else {
+    check_act_bf16_cl(*x, N, C, H, W, who);
+  }
+  TORCH_CHECK(bdbnn_dgrad2_supported(H, W, (int)C, K) != 0, who,
+              ": unsupported shape");
+  at::Tensor ac = acc_as_bf16_cl(acc, N, C, H, W, who);
+  auto dx = empty_dx(g, N, C, H, W);
+  int rc = bdbnn_conv_dgrad2(
+      g.data_ptr(), wd.data_ptr(),
+      mp ? (const uint32_t*)mp->data_ptr<int>() : nullptr,
+      x ? x->data_ptr() : nullptr, dx.data_ptr(),
+      ac.defined() ? ac.data_ptr() : nullptr, (int)mode, (float)t, (float)k,
+      N, H, W, (int)C, K, cur_stream());
+  TORCH_CHECK(rc == 0, who, ": launch rejected the shape");
+  return dx;
 }
 
 at::Tensor conv_dgrad2(const at::Tensor& g, const at::Tensor& wd,
                        const at::Tensor& mp, int64_t C,
                        const c10::optional<at::Tensor>& acc) {
-  TORCH_CHECK(g.is_cuda() && g.dim() == 4 &&
-                  g.scalar_type() == at::kBFloat16 &&
-                  g.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_dgrad2: bf16 channels_last grad");
-  int N = (int)g.size(0), K = (int)g.size(1);
-  int H = (int)g.size(2), W = (int)g.size(3);
-  TORCH_CHECK(wd.dim() == 3 && wd.size(0) == 9 && wd.size(1) == C &&
-                  wd.size(2) == K && wd.scalar_type() == at::kBFloat16,
-              "conv_dgrad2: decoded weights [9][C][K] bf16");
-  TORCH_CHECK(mp.size(-1) == C / 32 &&
-                  mp.numel() == (int64_t)N * H * W * (C / 32),
-              "conv_dgrad2: mask bitplane [...P...][C/32]");
-  TORCH_CHECK(dgrad2_ok(H, W, (int)C, K), "conv_dgrad2: unsupported shape");
-  const void* accp = nullptr;
-  at::Tensor ac;
-  if (acc.has_value()) {
-    ac = acc->scalar_type() == at::kBFloat16
-             ? acc->contiguous(at::MemoryFormat::ChannelsLast)
-             : acc->to(at::kBFloat16)
-                   .contiguous(at::MemoryFormat::ChannelsLast);
-    TORCH_CHECK(ac.dim() == 4 && ac.size(0) == N && ac.size(1) == C &&
-                    ac.size(2) == H && ac.size(3) == W,
-                "conv_dgrad2: acc shape must match dx (N,C,H,W)");
-    accp = ac.data_ptr();
-  }
-  auto dx = at::empty({N, C, H, W}, g.options(),
-                      at::MemoryFormat::ChannelsLast);
-  int rc = bdbnn_conv_dgrad2(g.data_ptr(), wd.data_ptr(),
-                             (const uint32_t*)mp.data_ptr<int>(),
-                             dx.data_ptr(), accp, N, H, W, (int)C, K,
-                             cur_stream());
-  TORCH_CHECK(rc == 0, "conv_dgrad2: launch rejected the shape");
-  return dx;
+  return conv_dgrad2_impl(g, wd, &mp, nullptr, C, 0, 0.0, 0.0, acc,
+                          "conv_dgrad2");
 }
 
-// value-mask variant for the ReAct-polynomial (mode 1) and EDE (mode 2)
-// activation gradients: the mask is evaluated from the saved bf16
-// activation x in the epilogue instead of read from a bitplane
 at::Tensor conv_dgrad2_x(const at::Tensor& g, const at::Tensor& wd,
                          const at::Tensor& x, int64_t C, int64_t mode,
                          double t, double k,
                          const c10::optional<at::Tensor>& acc) {
   TORCH_CHECK(mode == 1 || mode == 2,
               "conv_dgrad2_x: mode must be 1 (approx) or 2 (EDE)");
-  TORCH_CHECK(g.is_cuda() && g.dim() == 4 &&
-                  g.scalar_type() == at::kBFloat16 &&
-                  g.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_dgrad2_x: bf16 channels_last grad");
-  int N = (int)g.size(0), K = (int)g.size(1);
-  int H = (int)g.size(2), W = (int)g.size(3);
-  TORCH_CHECK(wd.is_cuda() && wd.dim() == 3 && wd.size(0) == 9 &&
-                  wd.size(1) == C && wd.size(2) == K &&
-                  wd.scalar_type() == at::kBFloat16 && wd.is_contiguous(),
-              "conv_dgrad2_x: decoded weights [9][C][K] bf16");
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
-                  x.scalar_type() == at::kBFloat16 &&
-                  x.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_dgrad2_x: bf16 channels_last activation");
-  TORCH_CHECK(x.size(0) == N && x.size(1) == C && x.size(2) == H &&
-                  x.size(3) == W,
-              "conv_dgrad2_x: x shape must match dx (N,C,H,W)");
-  TORCH_CHECK(dgrad2_ok(H, W, (int)C, K),
-              "conv_dgrad2_x: unsupported shape");
-  const void* accp = nullptr;
-  at::Tensor ac;
-  if (acc.has_value()) {
-    ac = acc->scalar_type() == at::kBFloat16
-             ? acc->contiguous(at::MemoryFormat::ChannelsLast)
-             : acc->to(at::kBFloat16)
-                   .contiguous(at::MemoryFormat::ChannelsLast);
-    TORCH_CHECK(ac.is_cuda() && ac.dim() == 4 && ac.size(0) == N &&
-                    ac.size(1) == C && ac.size(2) == H && ac.size(3) == W,
-                "conv_dgrad2_x: acc shape must match dx (N,C,H,W)");
-    accp = ac.data_ptr();
-  }
-  auto dx = at::empty({N, C, H, W}, g.options(),
-                      at::MemoryFormat::ChannelsLast);
-  int rc = bdbnn_conv_dgrad2_x(g.data_ptr(), wd.data_ptr(), x.data_ptr(),
-                               dx.data_ptr(), accp, (int)mode, (float)t,
-                               (float)k, N, H, W, (int)C, K, cur_stream());
-  TORCH_CHECK(rc == 0, "conv_dgrad2_x: launch rejected the shape");
-  return dx;
-}
-
-// ---------------- MFMA wgrad v2 (hot path) ----------------
-
-at::Tensor repack_cplane(const at::Tensor& xp, int64_t C, int64_t W) {
-  TORCH_CHECK(xp.is_cuda() && xp.dim() == 4 && xp.size(3) == (C + 31) / 32,
-              "repack_cplane: packed activations [N][H][W][CW]");
-  TORCH_CHECK(xp.size(2) == W, "repack_cplane: W mismatch");
-  TORCH_CHECK(W <= 64, "repack_cplane: W <= 64");
-  int NH = (int)(xp.size(0) * xp.size(1));
-  auto xcp = at::empty({C, NH}, xp.options().dtype(at::kLong));
-  bdbnn_repack_cplane((const uint32_t*)xp.data_ptr<int>(),
-                      (uint64_t*)xcp.data_ptr<int64_t>(), NH, (int)W,
-                      (int)C, (int)xp.size(3), cur_stream());
-  return xcp;
+  return conv_dgrad2_impl(g, wd, nullptr, &x, C, mode, t, k, acc,
+                          "conv_dgrad2_x");
 }
 
 at::Tensor conv_wgrad2(const at::Tensor& g, const at::Tensor& xcp,
                        int64_t C) {
-  TORCH_CHECK(g.is_cuda() && g.dim() == 4 &&
-                  g.scalar_type() == at::kBFloat16 &&
-                  g.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_wgrad2: bf16 channels_last grad");
+  check_grad_bf16_cl(g, "conv_wgrad2");
   int N = (int)g.size(0), K = (int)g.size(1);
   int H = (int)g.size(2), W = (int)g.size(3);
   TORCH_CHECK(xcp.dim() == 2 && xcp.size(0) == C &&
@@ -865,23 +926,7 @@ at::Tensor conv_wgrad2(const at::Tensor& g, const at::Tensor& xcp,
   return dwT;
 }
 
-at::Tensor wgrad_finish(const at::Tensor& dwT, const at::Tensor& w) {
-  TORCH_CHECK(w.is_cuda() && w.dim() == 4 && w.size(2) == 3 &&
-                  w.size(3) == 3 && w.scalar_type() == at::kFloat,
-              "wgrad_finish: fp32 [K][C][3][3] latent weights");
-  int K = (int)w.size(0), C = (int)w.size(1);
-  TORCH_CHECK(dwT.dim() == 4 && dwT.size(1) == 9 && dwT.size(2) == C &&
-                  dwT.size(3) == K && dwT.scalar_type() == at::kFloat,
-              "wgrad_finish: dwT [nslab][9][C][K] fp32");
-  auto wc = w.contiguous();
-  auto dw = at::empty_like(wc);
-  bdbnn_wgrad_finish(dwT.contiguous().data_ptr<float>(),
-                     wc.data_ptr<float>(), dw.data_ptr<float>(), C, K,
-                     (int)dwT.size(0), cur_stream());
-  return dw;
-}
-
-// ---------------- MFMA backward, stride 2 (csrc/conv_bwd_s2.hip) ---------
+// ---------------- stride 2 (3x3/s2/p1, 1x1/s2/p0) ----------------
 
 // shape predicates of the stride-2 path; H, W are the INPUT (dx) size,
 // ks the kernel size (3 -> pad 1, 1 -> pad 0).  dgrad2_s2_ok: what the
@@ -905,27 +950,6 @@ static bool dgrad2_s2_routed(int64_t H, int64_t W, int64_t C, int64_t K,
                                    (int)ks) != 0;
 }
 
-at::Tensor dgrad_weight_decode_1x1(const at::Tensor& wp,
-                                   const at::Tensor& alpha, int64_t C) {
-  TORCH_CHECK(wp.is_cuda() && wp.dim() == 4 && wp.size(1) == 1 &&
-                  wp.size(2) == 1 && wp.scalar_type() == at::kInt,
-              "dgrad_weight_decode_1x1: wp must be packed 1x1 weights "
-              "[K][1][1][CW] int32");
-  int K = (int)wp.size(0);
-  TORCH_CHECK(K % 8 == 0 && C % 32 == 0 && wp.size(3) == C / 32,
-              "dgrad_weight_decode_1x1: C must match wp (K%8, C%32)");
-  TORCH_CHECK(alpha.is_cuda() && alpha.scalar_type() == at::kFloat &&
-                  alpha.numel() == K,
-              "dgrad_weight_decode_1x1: alpha must be fp32 [K]");
-  auto wd = at::empty({1, C, K}, wp.options().dtype(at::kBFloat16));
-  auto al = alpha.contiguous();
-  auto wpc = wp.contiguous();
-  bdbnn_dgrad_wdec_1x1((const uint32_t*)wpc.data_ptr<int>(),
-                       al.data_ptr<float>(), wd.data_ptr(), (int)C, K,
-                       cur_stream());
-  return wd;
-}
-
 // dx of a 3x3/s2/p1 (wd [9][C][K]) or 1x1/s2/p0 (wd [1][C][K]) conv at
 // input size (H, W); mode 0 masks with the bitplane mp, modes 1/2 with
 // the value mask of the saved activation x
@@ -934,11 +958,8 @@ at::Tensor conv_dgrad2_s2(const at::Tensor& g, const at::Tensor& wd,
                           const c10::optional<at::Tensor>& mp,
                           const c10::optional<at::Tensor>& x, double t,
                           double k, const c10::optional<at::Tensor>& acc) {
-  TORCH_CHECK(g.is_cuda() && g.dim() == 4 &&
-                  g.scalar_type() == at::kBFloat16,
-              "conv_dgrad2_s2: g must be a 4-D bf16 CUDA tensor");
-  TORCH_CHECK(g.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_dgrad2_s2: g must be channels_last");
+  const char* who = "conv_dgrad2_s2";
+  check_grad_bf16_cl(g, who);
   int N = (int)g.size(0), K = (int)g.size(1);
   TORCH_CHECK(wd.is_cuda() && wd.dim() == 3 &&
                   wd.scalar_type() == at::kBFloat16 && wd.is_contiguous(),
@@ -959,7 +980,6 @@ at::Tensor conv_dgrad2_s2(const at::Tensor& g, const at::Tensor& wd,
               "(EDE)");
   const uint32_t* mp_ptr = nullptr;
   const void* x_ptr = nullptr;
-  at::Tensor mpc;
   if (mode == 0) {
     TORCH_CHECK(mp.has_value() && !x.has_value(),
                 "conv_dgrad2_s2: mode 0 needs mp and x=None");
@@ -972,63 +992,23 @@ at::Tensor conv_dgrad2_s2(const at::Tensor& g, const at::Tensor& wd,
   } else {
     TORCH_CHECK(x.has_value() && !mp.has_value(),
                 "conv_dgrad2_s2: modes 1/2 need x and mp=None");
-    TORCH_CHECK(x->is_cuda() && x->dim() == 4 &&
-                    x->scalar_type() == at::kBFloat16,
-                "conv_dgrad2_s2: x must be a 4-D bf16 CUDA tensor");
-    TORCH_CHECK(x->is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv_dgrad2_s2: x must be channels_last");
-    TORCH_CHECK(x->size(0) == N && x->size(1) == C && x->size(2) == H &&
-                    x->size(3) == W,
-                "conv_dgrad2_s2: x shape must match dx (N,C,H,W)");
+    check_act_bf16_cl(*x, N, C, H, W, who);
     x_ptr = x->data_ptr();
   }
-  const void* accp = nullptr;
-  at::Tensor ac;
-  if (acc.has_value()) {
-    ac = acc->scalar_type() == at::kBFloat16
-             ? acc->contiguous(at::MemoryFormat::ChannelsLast)
-             : acc->to(at::kBFloat16)
-                   .contiguous(at::MemoryFormat::ChannelsLast);
-    TORCH_CHECK(ac.is_cuda() && ac.dim() == 4 && ac.size(0) == N &&
-                    ac.size(1) == C && ac.size(2) == H && ac.size(3) == W,
-                "conv_dgrad2_s2: acc shape must match dx (N,C,H,W)");
-    accp = ac.data_ptr();
-  }
-  auto dx = at::empty({N, C, H, W}, g.options(),
-                      at::MemoryFormat::ChannelsLast);
+  at::Tensor ac = acc_as_bf16_cl(acc, N, C, H, W, who);
+  auto dx = empty_dx(g, N, C, H, W);
   int rc = bdbnn_conv_dgrad2_s2(g.data_ptr(), wd.data_ptr(), mp_ptr, x_ptr,
-                                dx.data_ptr(), accp, ks, (int)mode,
-                                (float)t, (float)k, N, (int)H, (int)W,
-                                (int)C, K, cur_stream());
+                                dx.data_ptr(),
+                                ac.defined() ? ac.data_ptr() : nullptr, ks,
+                                (int)mode, (float)t, (float)k, N, (int)H,
+                                (int)W, (int)C, K, cur_stream());
   TORCH_CHECK(rc == 0, "conv_dgrad2_s2: launch rejected the shape");
   return dx;
 }
 
-at::Tensor repack_cplane_s2(const at::Tensor& xp, int64_t C, int64_t H,
-                            int64_t W) {
-  TORCH_CHECK(xp.is_cuda() && xp.dim() == 4 &&
-                  xp.scalar_type() == at::kInt && xp.is_contiguous(),
-              "repack_cplane_s2: xp must be contiguous int32 [N][H][W][CW]");
-  TORCH_CHECK(xp.size(3) == (C + 31) / 32,
-              "repack_cplane_s2: C does not match xp's word count");
-  TORCH_CHECK(xp.size(1) == H && xp.size(2) == W,
-              "repack_cplane_s2: H, W do not match xp");
-  TORCH_CHECK(W >= 1 && W <= 64, "repack_cplane_s2: W must be <= 64");
-  int NH = (int)(xp.size(0) * xp.size(1));
-  auto planes = at::empty({C, NH}, xp.options().dtype(at::kLong));
-  bdbnn_repack_cplane_s2((const uint32_t*)xp.data_ptr<int>(),
-                         (uint64_t*)planes.data_ptr<int64_t>(), NH, (int)W,
-                         (int)C, (int)xp.size(3), cur_stream());
-  return planes;
-}
-
 at::Tensor conv_wgrad2_s2(const at::Tensor& g, const at::Tensor& planes,
                           int64_t C, int64_t H, int64_t W, int64_t ks) {
-  TORCH_CHECK(g.is_cuda() && g.dim() == 4 &&
-                  g.scalar_type() == at::kBFloat16,
-              "conv_wgrad2_s2: g must be a 4-D bf16 CUDA tensor");
-  TORCH_CHECK(g.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_wgrad2_s2: g must be channels_last");
+  check_grad_bf16_cl(g, "conv_wgrad2_s2");
   int N = (int)g.size(0), K = (int)g.size(1);
   TORCH_CHECK(dgrad2_s2_ok(H, W, C, K, ks),
               "conv_wgrad2_s2: unsupported shape (H, W, C, K, ks)");
@@ -1052,25 +1032,6 @@ at::Tensor conv_wgrad2_s2(const at::Tensor& g, const at::Tensor& planes,
                                 (int)W, (int)C, K, cur_stream());
   TORCH_CHECK(rc == 0, "conv_wgrad2_s2: launch rejected the shape");
   return dwT;
-}
-
-at::Tensor wgrad_finish_s2(const at::Tensor& dwT, const at::Tensor& w) {
-  TORCH_CHECK(w.is_cuda() && w.dim() == 4 && w.size(2) == w.size(3) &&
-                  (w.size(2) == 3 || w.size(2) == 1) &&
-                  w.scalar_type() == at::kFloat,
-              "wgrad_finish_s2: w must be fp32 [K][C][ks][ks], ks in {1,3}");
-  int K = (int)w.size(0), C = (int)w.size(1);
-  int T = (int)(w.size(2) * w.size(3));
-  TORCH_CHECK(dwT.is_cuda() && dwT.dim() == 4 && dwT.size(1) == T &&
-                  dwT.size(2) == C && dwT.size(3) == K &&
-                  dwT.scalar_type() == at::kFloat,
-              "wgrad_finish_s2: dwT must be fp32 [nslab][ks*ks][C][K]");
-  auto wc = w.contiguous();
-  auto dw = at::empty_like(wc);
-  bdbnn_wgrad_finish_s2(dwT.contiguous().data_ptr<float>(),
-                        wc.data_ptr<float>(), dw.data_ptr<float>(), C, K, T,
-                        (int)dwT.size(0), cur_stream());
-  return dw;
 }
 
 // ---------------- experimental MFMA dgrad (v1, kept for A/B) -------------
@@ -1271,7 +1232,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "packed bits -> mirrored transposed +-alpha bf16 [9][C][K]");
   m.def("dgrad2_supported",
         [](int64_t H, int64_t W, int64_t C, int64_t K) {
-          return dgrad2_ok((int)H, (int)W, (int)C, (int)K);
+          return bdbnn_dgrad2_supported((int)H, (int)W, (int)C, (int)K) !=
+                 0;
         },
         "shape support predicate for conv_dgrad2");
   m.def("conv_wgrad2", &conv_wgrad2,

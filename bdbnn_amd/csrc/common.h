@@ -24,6 +24,15 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
   return uint16_t((v.u + rounding) >> 16);
 }
 
+// XCD-aware block remap (8 XCDs with private L2s): consecutive remapped
+// ids run on ONE XCD, so neighbouring tiles (sharing input rows) land on
+// one L2.  Bijective for any grid size.
+__device__ __forceinline__ int bd_xcd_remap(int wg, int nwg) {
+  int q = nwg / 8, r = nwg % 8;
+  int xcd = wg % 8, idx = wg / 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
 // Grid-stride helper
 #define GRID_STRIDE(i, n)                                            \
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;   \

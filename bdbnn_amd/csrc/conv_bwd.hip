@@ -75,14 +75,7 @@ __global__ __launch_bounds__(512, 2) void conv_dgrad2_kernel(
   constexpr int PIECES = NHE * 8;             // 16-B staging pieces
   constexpr int PPT = (PIECES + 511) / 512;   // pieces per thread
 
-  // XCD-aware bijective remap (8 XCDs with private L2s)
-  int nwg = gridDim.x;
-  int wg = blockIdx.x;
-  {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, idx = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = bd_xcd_remap(blockIdx.x, gridDim.x);
   const int rb_m = wg % nb_m;               // which m-tile RANGE
   const int c_blk = wg / nb_m;
   const int c0 = c_blk * DG2_BN;
@@ -202,7 +195,7 @@ __global__ __launch_bounds__(512, 2) void conv_dgrad2_kernel(
 
   // epilogue: clip-STE mask from the packed bitplane (MODE 0) or value
   // mask of the saved activation (MODE 1/2), bf16 store.
-  // C/D layout: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
+  // C/D layout: col = lane&31, row = mfma32_cd_row(reg, lane>>5).
   const int ccol = c0 + wc + lrow;
   const int cw_word = ccol >> 5;
   const int cbit = ccol & 31;
@@ -212,14 +205,14 @@ __global__ __launch_bounds__(512, 2) void conv_dgrad2_kernel(
     _Pragma("unroll")                                                     \
     for (int half = 0; half < 2; ++half) {                                \
       const f32x16& acc = half ? acc1 : acc0;                             \
-      const int mbase = wm0 + half * 32 + 4 * lk8;                        \
+      const int mbase = wm0 + half * 32;                                  \
       int pixr[16];                                                       \
       uint32_t mpw[16];                                                   \
       uint16_t xv[16];                                                    \
       uint16_t av[16];                                                    \
       _Pragma("unroll")                                                   \
       for (int reg = 0; reg < 16; ++reg)                                  \
-        pixr[reg] = tab_out[tb][mbase + (reg & 3) + 8 * (reg >> 2)];      \
+        pixr[reg] = tab_out[tb][mbase + mfma32_cd_row(reg, lk8)];         \
       /* batch-issue the mask/skip-grad loads (one waitcnt for all,   */ \
       /* instead of a load-use pair per element that serializes the   */ \
       /* whole epilogue behind HBM latency once per tile).  pix<0     */ \
@@ -325,69 +318,69 @@ __global__ __launch_bounds__(512, 2) void conv_dgrad2_kernel(
 
 // ---------------- host launcher ----------------
 
+// THE (WP, RB, GB) table of conv_dgrad2_kernel: calls f(BwdClass) for the
+// padded-width class of an (H, W) image, -1 where there is none.
+template <class F>
+static int dgrad2_class(int H, int W, F f) {
+  if (W <= 8) return H > 8 ? -1 : f(BwdClass<8, 8, 4>{});
+  if (W <= 16) return f(BwdClass<16, 16, 1>{});
+  if (W <= 32) return f(BwdClass<32, 8, 1>{});
+  return f(BwdClass<64, 4, 1>{});
+}
+
+// shapes the launcher below accepts — its own condition, also the
+// routing predicate python sees (dgrad2_supported)
+extern "C" int bdbnn_dgrad2_supported(int H, int W, int C, int K) {
+  if (C % 64 || K % 64 || W > 64) return 0;
+  return dgrad2_class(H, W, [](auto) { return 0; }) == 0;
+}
+
 template <int MODE>
 static int dgrad2_launch(const void* g, const void* wd, const uint32_t* mp,
                          void* dx, const void* accp, const void* xin,
                          float et, float ek, int N, int H, int W, int C,
                          int K, hipStream_t stream) {
-  if (C % 64 || K % 64 || W > 64) return -1;
-  Dgrad2Params p;
-  p.N = N; p.H = H; p.W = W; p.C = C; p.K = K;
-  p.CW = C / 32;
-  int grid_m;
-#define LAUNCH(WPV, RBV, GBV)                                             \
-  {                                                                       \
-    p.bands_per_image = (H + (RBV)-1) / (RBV);                            \
-    p.total_slots = N * p.bands_per_image;                                \
-    grid_m = (p.total_slots + (GBV)-1) / (GBV);                           \
-    int n_ctile = C / DG2_BN;                                             \
-    /* 1 block/CU resident (LDS-bound): ~2 ranges per CU for tail      */ \
-    /* balance, contiguous m-tiles per block for halo L2 reuse         */ \
-    int nb_m = bd_min(grid_m, bd_min(512, 768 / n_ctile));                \
-    int tpb = (grid_m + nb_m - 1) / nb_m;                                 \
-    nb_m = (grid_m + tpb - 1) / tpb;                                      \
-    dim3 grid(nb_m * n_ctile);                                            \
-    if (accp)                                                             \
-      conv_dgrad2_kernel<WPV, RBV, GBV, true, MODE>                       \
-          <<<grid, 512, 0, stream>>>(                                     \
-              (const __bf16*)g, (const __bf16*)wd, mp, (__bf16*)dx,       \
-              (const __bf16*)accp, (const __bf16*)xin, et, ek, p, grid_m, \
-              nb_m, tpb);                                                 \
-    else                                                                  \
-      conv_dgrad2_kernel<WPV, RBV, GBV, false, MODE>                      \
-          <<<grid, 512, 0, stream>>>(                                     \
-              (const __bf16*)g, (const __bf16*)wd, mp, (__bf16*)dx,       \
-              nullptr, (const __bf16*)xin, et, ek, p, grid_m, nb_m, tpb); \
-    return 0;                                                             \
-  }
-  if (W <= 8) {
-    if (H > 8) return -1;
-    LAUNCH(8, 8, 4);
-  } else if (W <= 16) {
-    LAUNCH(16, 16, 1);
-  } else if (W <= 32) {
-    LAUNCH(32, 8, 1);
-  } else {
-    LAUNCH(64, 4, 1);
-  }
-#undef LAUNCH
+  if (!bdbnn_dgrad2_supported(H, W, C, K)) return -1;
+  return dgrad2_class(H, W, [&](auto cls) {
+    using G = decltype(cls);
+    Dgrad2Params p;
+    p.N = N; p.H = H; p.W = W; p.C = C; p.K = K;
+    p.CW = C / 32;
+    p.bands_per_image = (H + G::RB - 1) / G::RB;
+    p.total_slots = N * p.bands_per_image;
+    int grid_m = (p.total_slots + G::GB - 1) / G::GB;
+    int n_ctile = C / DG2_BN;
+    // 1 block/CU resident (LDS-bound): ~2 ranges per CU for tail
+    // balance, contiguous m-tiles per block for halo L2 reuse
+    int nb_m = bd_min(grid_m, bd_min(512, 768 / n_ctile));
+    int tpb = (grid_m + nb_m - 1) / nb_m;
+    nb_m = (grid_m + tpb - 1) / tpb;
+    dim3 grid(nb_m * n_ctile);
+    if (accp)
+      conv_dgrad2_kernel<G::WP, G::RB, G::GB, true, MODE>
+          <<<grid, 512, 0, stream>>>(
+              (const __bf16*)g, (const __bf16*)wd, mp, (__bf16*)dx,
+              (const __bf16*)accp, (const __bf16*)xin, et, ek, p, grid_m,
+              nb_m, tpb);
+    else
+      conv_dgrad2_kernel<G::WP, G::RB, G::GB, false, MODE>
+          <<<grid, 512, 0, stream>>>(
+              (const __bf16*)g, (const __bf16*)wd, mp, (__bf16*)dx,
+              nullptr, (const __bf16*)xin, et, ek, p, grid_m, nb_m, tpb);
+    return 0;
+  });
 }
 
+// mode 0: mp = clip-STE bitplane, x unused; mode 1 (ReAct polynomial) /
+// 2 (EDE(t, k)): x = saved bf16 NHWC activation (dx's shape), mp unused
 extern "C" int bdbnn_conv_dgrad2(const void* g, const void* wd,
-                                 const uint32_t* mp, void* dx,
-                                 const void* accp, int N, int H,
-                                 int W, int C, int K, hipStream_t stream) {
-  return dgrad2_launch<0>(g, wd, mp, dx, accp, nullptr, 0.f, 0.f, N, H, W,
-                          C, K, stream);
-}
-
-// value-mask variant: x is the saved bf16 NHWC activation (same shape as
-// dx); mode 1 = ReAct polynomial, 2 = EDE(t, k)
-extern "C" int bdbnn_conv_dgrad2_x(const void* g, const void* wd,
-                                   const void* x, void* dx,
-                                   const void* accp, int mode, float t,
-                                   float k, int N, int H, int W, int C,
-                                   int K, hipStream_t stream) {
+                                 const uint32_t* mp, const void* x,
+                                 void* dx, const void* accp, int mode,
+                                 float t, float k, int N, int H, int W,
+                                 int C, int K, hipStream_t stream) {
+  if (mode == 0)
+    return dgrad2_launch<0>(g, wd, mp, dx, accp, nullptr, 0.f, 0.f, N, H, W,
+                            C, K, stream);
   if (mode == 1)
     return dgrad2_launch<1>(g, wd, nullptr, dx, accp, x, 0.f, 0.f, N, H, W,
                             C, K, stream);
@@ -398,27 +391,29 @@ extern "C" int bdbnn_conv_dgrad2_x(const void* g, const void* wd,
 }
 
 // ---------------- mirrored/transposed weight decode ----------------
-// wp: uint32 [K][9][CW] inverted bits (csrc/pack.hip: bit 1 <=> w < 0),
-// alpha: fp32 [K]  ->  wd bf16 [9][C][K], wd[t][c][k] = +-alpha_k with
-// the tap MIRRORED (t reads w[k,c,2-dy,2-dx]).
+// wp: uint32 [K][NT][CW] inverted bits (csrc/pack.hip: bit 1 <=> w < 0),
+// alpha: fp32 [K]  ->  wd bf16 [NT][C][K], wd[t][c][k] = +-alpha_k with
+// the tap MIRRORED (NT = 9: t reads w[k,c,2-dy,2-dx]; NT = 1: the one tap
+// of a 1x1 conv, nothing to mirror).
+template <int NT>
 __global__ void dgrad_wdec_kernel(const uint32_t* __restrict__ wp,
                                   const float* __restrict__ alpha,
                                   __bf16* __restrict__ wd, int C, int K,
                                   int CW) {
   // one thread per 8 outputs along k at fixed (t, c)
-  int64_t total = (int64_t)9 * C * (K / 8);
+  int64_t total = (int64_t)NT * C * (K / 8);
   GRID_STRIDE(i, total) {
     int k8 = int(i % (K / 8));
     int64_t rem = i / (K / 8);
-    int c = int(rem % C);
-    int t = int(rem / C);
-    int tm = 8 - t;                       // mirrored tap
+    int c = NT == 1 ? int(rem) : int(rem % C);
+    int t = NT == 1 ? 0 : int(rem / C);
+    int tm = NT - 1 - t;                  // mirrored tap
     int cw = c >> 5, cb = c & 31;
     __bf16 v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       int k = k8 * 8 + j;
-      uint32_t bits = wp[((int64_t)k * 9 + tm) * CW + cw];
+      uint32_t bits = wp[((int64_t)k * NT + tm) * CW + cw];
       float al = alpha[k];
       v[j] = (__bf16)((bits >> cb) & 1 ? -al : al);
     }
@@ -426,13 +421,18 @@ __global__ void dgrad_wdec_kernel(const uint32_t* __restrict__ wp,
   }
 }
 
+// nt = 9 (3x3) or 1 (1x1)
 extern "C" void bdbnn_dgrad_wdec(const uint32_t* wp, const float* alpha,
-                                 void* wd, int C, int K,
+                                 void* wd, int C, int K, int nt,
                                  hipStream_t stream) {
-  int64_t total = (int64_t)9 * C * (K / 8);
+  int64_t total = (int64_t)nt * C * (K / 8);
   int blocks = (int)bd_min<int64_t>((total + 255) / 256, 4096);
-  dgrad_wdec_kernel<<<blocks, 256, 0, stream>>>(wp, alpha, (__bf16*)wd, C,
-                                                K, C / 32);
+  if (nt == 9)
+    dgrad_wdec_kernel<9><<<blocks, 256, 0, stream>>>(wp, alpha, (__bf16*)wd,
+                                                     C, K, C / 32);
+  else
+    dgrad_wdec_kernel<1><<<blocks, 256, 0, stream>>>(wp, alpha, (__bf16*)wd,
+                                                     C, K, C / 32);
 }
 
 // ======================= wgrad v2 =======================
@@ -511,12 +511,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad2_kernel(
   __shared__ uint64_t xbits[NBITS];
   __shared__ unsigned char xvalid[NBITS];  // 0 = pad row (decode to 0)
 
-  // ---- byte -> 8 x (+-1) LUT (bit 1 <=> x >= 0 <=> +1) ----
-  for (int b = tid; b < 256; b += 512) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      lut[b][j] = (__bf16)(((b >> j) & 1) ? 1.f : -1.f);
-  }
+  wgrad2_fill_sign_lut(lut, tid);
 
   // ---- wave decomposition: quad (c-half, k-half) x m-split ----
   const int wid = tid >> 6, lane = tid & 63;
@@ -760,84 +755,74 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad2_kernel(
   }
 
   // ---- m-split combine + plain coalesced slab store ----
-  // C/D layout: col j (k) = lane&31, row (c) = (reg&3)+8*(reg>>2)+4*lhalf
-  const int quad = wid & 3;
-  float* slab = dwT + (int64_t)split_id * 9 * p.C * p.K;
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    __syncthreads();
-    if (ms_grp == 1) {
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        int row = (reg & 3) + 8 * (reg >> 2) + 4 * lhalf;
-        red[quad][row][lrow] = acc[t][reg];
-      }
-    }
-    __syncthreads();
-    if (ms_grp == 0) {
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        int row = (reg & 3) + 8 * (reg >> 2) + 4 * lhalf;
-        float v = acc[t][reg] + red[quad][row][lrow];
-        slab[((int64_t)t * p.C + c0 + qc * 32 + row) * p.K + k0 +
-             qk * 32 + lrow] = v;
-      }
-    }
-  }
+  wgrad2_combine_store<9>(acc, red, dwT + (int64_t)split_id * 9 * p.C * p.K,
+                          p.C, p.K, c0, k0, wid, lane);
 }
 
-// split (= slab count) mirrored for the host-side dwT allocation
-extern "C" int bdbnn_wgrad2_nslab(int N, int H, int W, int C, int K) {
-  if (C % 64 || K % 64 || W > 64) return -1;
+// THE (WP, RB, GB) table of conv_wgrad2_kernel: calls f(BwdClass) for the
+// padded-width class of an (H, W) image.
+template <class F>
+static int wgrad2_class(int H, int W, F f) {
+  if (W <= 8 && H <= 8) return f(BwdClass<8, 8, 2>{});
+  if (W <= 16) return f(BwdClass<16, 8, 1>{});
+  if (W <= 32) return f(BwdClass<32, 4, 1>{});
+  return f(BwdClass<64, 2, 1>{});
+}
+
+static bool wgrad2_shape_ok(int W, int C, int K) {
+  return !(C % 64 || K % 64 || W > 64);
+}
+
+// chunking and m-split of a shape in class G.  The launcher and the
+// host-side slab count both take p.split from HERE: the kernel writes
+// exactly the slabs the caller allocated.
+template <class G>
+static Wgrad2Params wgrad2_params(G, int N, int H, int W, int C, int K) {
+  Wgrad2Params p;
+  p.N = N; p.H = H; p.W = W; p.C = C; p.K = K;
+  p.nh_rows = N * H;
+  p.bands_per_image = (H + G::RB - 1) / G::RB;
+  p.total_slots = N * p.bands_per_image;
+  p.total_chunks = (p.total_slots + G::GB - 1) / G::GB;
+  // LDS (~110-145 KB/block) admits ONE 512-thread block per CU: round
+  // the m-split so the grid is a whole multiple of 256 CUs (384 blocks
+  // = 1.5 dispatch rounds would idle half the chip for half the time)
   int grid_ck = (C / WG2_BC) * (K / WG2_BK);
-  int split = (256 + grid_ck - 1) / grid_ck;
-  int bands, total_chunks;
-  if (W <= 8 && H <= 8) {
-    bands = 1; total_chunks = (N + 1) / 2;
-  } else if (W <= 16) {
-    bands = (H + 7) / 8; total_chunks = N * bands;
-  } else if (W <= 32) {
-    bands = (H + 3) / 4; total_chunks = N * bands;
-  } else {
-    bands = (H + 1) / 2; total_chunks = N * bands;
-  }
-  return split < total_chunks ? split : total_chunks;
+  p.split = bd_min((256 + grid_ck - 1) / grid_ck, p.total_chunks);
+  return p;
+}
+
+// slab count (= split) for the host-side dwT allocation
+extern "C" int bdbnn_wgrad2_nslab(int N, int H, int W, int C, int K) {
+  if (!wgrad2_shape_ok(W, C, K)) return -1;
+  return wgrad2_class(H, W, [&](auto cls) {
+    return wgrad2_params(cls, N, H, W, C, K).split;
+  });
 }
 
 extern "C" int bdbnn_conv_wgrad2(const void* g, const uint64_t* xcp,
                                  float* dwT, int N, int H, int W, int C,
                                  int K, hipStream_t stream) {
-  if (C % 64 || K % 64 || W > 64) return -1;
-  Wgrad2Params p;
-  p.N = N; p.H = H; p.W = W; p.C = C; p.K = K;
-  p.nh_rows = N * H;
-  int grid_ck = (C / WG2_BC) * (K / WG2_BK);
-  // LDS (~110-145 KB/block) admits ONE 512-thread block per CU: round
-  // the m-split so the grid is a whole multiple of 256 CUs (384 blocks
-  // = 1.5 dispatch rounds would idle half the chip for half the time)
-  int split = (256 + grid_ck - 1) / grid_ck;
-  p.split = split;
-#define WLAUNCH(WPV, RBV, GBV)                                            \
-  {                                                                       \
-    p.bands_per_image = (H + (RBV)-1) / (RBV);                            \
-    p.total_slots = N * p.bands_per_image;                                \
-    p.total_chunks = (p.total_slots + (GBV)-1) / (GBV);                   \
-    if (p.split > p.total_chunks) p.split = p.total_chunks;               \
-    dim3 grid(grid_ck * p.split);                                         \
-    conv_wgrad2_kernel<WPV, RBV, GBV><<<grid, 512, 0, stream>>>(          \
-        (const __bf16*)g, xcp, dwT, p, grid_ck);                          \
-    return 0;                                                             \
-  }
-  if (W <= 8 && H <= 8) WLAUNCH(8, 8, 2)
-  else if (W <= 16) WLAUNCH(16, 8, 1)
-  else if (W <= 32) WLAUNCH(32, 4, 1)
-  else WLAUNCH(64, 2, 1)
-#undef WLAUNCH
+  if (!wgrad2_shape_ok(W, C, K)) return -1;
+  return wgrad2_class(H, W, [&](auto cls) {
+    using G = decltype(cls);
+    Wgrad2Params p = wgrad2_params(cls, N, H, W, C, K);
+    int grid_ck = (C / WG2_BC) * (K / WG2_BK);
+    dim3 grid(grid_ck * p.split);
+    conv_wgrad2_kernel<G::WP, G::RB, G::GB><<<grid, 512, 0, stream>>>(
+        (const __bf16*)g, xcp, dwT, p, grid_ck);
+    return 0;
+  });
 }
 
-// ---------------- padded c-plane repack ----------------
+// ---------------- c-plane repack ----------------
 // xp [P][CW] (bit c of word = sign of x[p, 32cw+c])  ->  xcp u64 rows
-// [C][N*H], row = W bits of one image row zero-padded to 64.
+// [C][N*H], one word per (c, image row), the W column bits zero-padded to
+// 64.  PARITY false (stride 1): bit x = column x.  PARITY true (stride
+// 2): bit r = column 2r (even columns, low word), bit 32+r = column 2r+1
+// (odd columns, high word); row parity is the row index's, so the four
+// parity planes are the two halves of the even and of the odd rows.
+template <bool PARITY>
 __global__ void repack_cplane_kernel(const uint32_t* __restrict__ xp,
                                      uint64_t* __restrict__ xcp, int NH,
                                      int W, int C, int CW) {
@@ -851,9 +836,10 @@ __global__ void repack_cplane_kernel(const uint32_t* __restrict__ xp,
     for (int c = 0; c < 32; ++c) acc[c] = 0;
     for (int x = 0; x < W; ++x) {
       uint32_t word = src[(int64_t)x * CW];
+      int pos = PARITY ? (x >> 1) + ((x & 1) << 5) : x;
 #pragma unroll
       for (int c = 0; c < 32; ++c)
-        acc[c] |= (uint64_t)((word >> c) & 1) << x;
+        acc[c] |= (uint64_t)((word >> c) & 1) << pos;
     }
 #pragma unroll
     for (int c = 0; c < 32; ++c) {
@@ -865,24 +851,30 @@ __global__ void repack_cplane_kernel(const uint32_t* __restrict__ xp,
 
 extern "C" void bdbnn_repack_cplane(const uint32_t* xp, uint64_t* xcp,
                                     int NH, int W, int C, int CW,
-                                    hipStream_t stream) {
+                                    bool parity, hipStream_t stream) {
   int64_t total = (int64_t)NH * CW;
   int blocks = (int)bd_min<int64_t>((total + 255) / 256, 8192);
-  repack_cplane_kernel<<<blocks, 256, 0, stream>>>(xp, xcp, NH, W, C, CW);
+  if (parity)
+    repack_cplane_kernel<true><<<blocks, 256, 0, stream>>>(xp, xcp, NH, W, C,
+                                                           CW);
+  else
+    repack_cplane_kernel<false><<<blocks, 256, 0, stream>>>(xp, xcp, NH, W,
+                                                            C, CW);
 }
 
 // ---------------- wgrad finish: slab sum + transpose + STE mask ----
-// dw[k][c][t] = sum_s dwT[s][t][c][k] * 1(|w[k][c][t]| <= 1)
-// (the slabs are conv_wgrad2's per-m-split-block partials; summing them
-// here replaces an end-of-kernel atomic storm on the tiny dwT)
+// dw[k][c][t] = sum_s dwT[s][t][c][k] * 1(|w[k][c][t]| <= 1), T taps
+// (the slabs are the wgrad kernels' per-m-split-block partials; summing
+// them here replaces an end-of-kernel atomic storm on the tiny dwT)
+template <int T>
 __global__ void wgrad_finish_kernel(const float* __restrict__ dwT,
                                     const float* __restrict__ w,
                                     float* __restrict__ dw, int C, int K,
                                     int nslab) {
-  int64_t stride = (int64_t)9 * C * K;
+  int64_t stride = (int64_t)T * C * K;
   GRID_STRIDE(i, stride) {
-    int t = int(i % 9);
-    int64_t rem = i / 9;
+    int t = int(i % T);
+    int64_t rem = i / T;
     int c = int(rem % C);
     int k = int(rem / C);
     float wv = w[i];
@@ -893,10 +885,16 @@ __global__ void wgrad_finish_kernel(const float* __restrict__ dwT,
   }
 }
 
+// T = 9 (3x3) or 1 (1x1)
 extern "C" void bdbnn_wgrad_finish(const float* dwT, const float* w,
-                                   float* dw, int C, int K, int nslab,
-                                   hipStream_t stream) {
-  int64_t total = (int64_t)9 * C * K;
+                                   float* dw, int C, int K, int T,
+                                   int nslab, hipStream_t stream) {
+  int64_t total = (int64_t)T * C * K;
   int blocks = (int)bd_min<int64_t>((total + 255) / 256, 8192);
-  wgrad_finish_kernel<<<blocks, 256, 0, stream>>>(dwT, w, dw, C, K, nslab);
+  if (T == 9)
+    wgrad_finish_kernel<9><<<blocks, 256, 0, stream>>>(dwT, w, dw, C, K,
+                                                       nslab);
+  else
+    wgrad_finish_kernel<1><<<blocks, 256, 0, stream>>>(dwT, w, dw, C, K,
+                                                       nslab);
 }

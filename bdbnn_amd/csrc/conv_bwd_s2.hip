@@ -74,14 +74,7 @@ __global__ __launch_bounds__(512, 2) void conv_dgrad2_s2_kernel(
   constexpr int PIECES = NHE * 8;             // 16-B staging pieces
   constexpr int PPT = (PIECES + 511) / 512;   // pieces per thread
 
-  // XCD-aware bijective remap (8 XCDs with private L2s)
-  int nwg = gridDim.x;
-  int wg = blockIdx.x;
-  {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, idx = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = bd_xcd_remap(blockIdx.x, gridDim.x);
   const int rb_m = wg % nb_m;               // which m-tile RANGE
   const int c_blk = wg / nb_m;
   const int c0 = c_blk * DS2_BN;
@@ -201,7 +194,7 @@ __global__ __launch_bounds__(512, 2) void conv_dgrad2_s2_kernel(
   *(uint4*)&blds[buf][b_c * DS2_BK + ((b_k8 ^ (b_c & 7)) << 3)] = breg;
 
   // epilogue: mask + (optional) skip grad, bf16 store, once per phase.
-  // C/D layout: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
+  // C/D layout: col = lane&31, row = mfma32_cd_row(reg, lane>>5).
   const int ccol = c0 + wc + lrow;
   const int cw_word = ccol >> 5;
   const int cbit = ccol & 31;
@@ -213,14 +206,13 @@ __global__ __launch_bounds__(512, 2) void conv_dgrad2_s2_kernel(
       const int py = ph >> 1, px = ph & 1;                                \
       /* 1x1: phases 1..3 have no tap -> plain 0 (or skip grad) */        \
       const bool live = (KS == 3) || ph == 0;                             \
-      const int mbase = wm0 + 4 * lk8;                                    \
       int pixr[16];                                                       \
       uint32_t mpw[16];                                                   \
       uint16_t xv[16];                                                    \
       uint16_t av[16];                                                    \
       _Pragma("unroll")                                                   \
       for (int reg = 0; reg < 16; ++reg) {                                \
-        int m = mbase + (reg & 3) + 8 * (reg >> 2);                       \
+        int m = wm0 + mfma32_cd_row(reg, lk8);                            \
         int base = tab_out[tb][m];                                        \
         int fl = tab_fl[tb][m];                                           \
         bool ok = base >= 0 && (!px || (fl & 1)) && (!py || (fl & 2));    \
@@ -436,40 +428,6 @@ extern "C" int bdbnn_conv_dgrad2_s2(const void* g, const void* wd,
   return -1;
 }
 
-// ---------------- 1x1 transposed weight decode ----------------
-// wp: uint32 [K][1][1][CW] inverted bits (bit 1 <=> w < 0), alpha fp32
-// [K]  ->  wd bf16 [1][C][K], wd[0][c][k] = +-alpha_k.
-__global__ void dgrad_wdec_1x1_kernel(const uint32_t* __restrict__ wp,
-                                      const float* __restrict__ alpha,
-                                      __bf16* __restrict__ wd, int C, int K,
-                                      int CW) {
-  // one thread per 8 outputs along k at fixed c
-  int64_t total = (int64_t)C * (K / 8);
-  GRID_STRIDE(i, total) {
-    int k8 = int(i % (K / 8));
-    int c = int(i / (K / 8));
-    int cw = c >> 5, cb = c & 31;
-    __bf16 v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      int k = k8 * 8 + j;
-      uint32_t bits = wp[(int64_t)k * CW + cw];
-      float al = alpha[k];
-      v[j] = (__bf16)((bits >> cb) & 1 ? -al : al);
-    }
-    *(uint4*)&wd[(int64_t)c * K + k8 * 8] = *(uint4*)v;
-  }
-}
-
-extern "C" void bdbnn_dgrad_wdec_1x1(const uint32_t* wp, const float* alpha,
-                                     void* wd, int C, int K,
-                                     hipStream_t stream) {
-  int64_t total = (int64_t)C * (K / 8);
-  int blocks = (int)bd_min<int64_t>((total + 255) / 256, 4096);
-  dgrad_wdec_1x1_kernel<<<blocks, 256, 0, stream>>>(wp, alpha, (__bf16*)wd,
-                                                    C, K, C / 32);
-}
-
 // ======================= wgrad, stride 2 =======================
 //
 //   dwT[t][c][k] = sum_m X_t[c][m] * g[m][k],   m = (n, oy, ox)
@@ -531,12 +489,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad2_s2_kernel(
   __shared__ uint64_t xbits64[B32 ? 1 : NBITS];
   __shared__ uint32_t xbits32[B32 ? NBITS : 1];
 
-  // ---- byte -> 8 x (+-1) LUT (bit 1 <=> x >= 0 <=> +1) ----
-  for (int b = tid; b < 256; b += 512) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      lut[b][j] = (__bf16)(((b >> j) & 1) ? 1.f : -1.f);
-  }
+  wgrad2_fill_sign_lut(lut, tid);
 
   // ---- wave decomposition: quad (c-half, k-half) x m-split ----
   const int wid = tid >> 6, lane = tid & 63;
@@ -759,32 +712,10 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad2_s2_kernel(
   }
 
   // ---- m-split combine + plain coalesced slab store ----
-  // C/D layout: col j (k) = lane&31, row (c) = (reg&3)+8*(reg>>2)+4*lhalf
   // (the scratch aliases X: every X read retired at the barrier above)
-  float(*red)[32][32] = (float(*)[32][32])X;
-  const int quad = wid & 3;
-  float* slab = dwT + (int64_t)split_id * NT * p.C * p.K;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    __syncthreads();
-    if (ms_grp == 1) {
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        int row = (reg & 3) + 8 * (reg >> 2) + 4 * lhalf;
-        red[quad][row][lrow] = acc[t][reg];
-      }
-    }
-    __syncthreads();
-    if (ms_grp == 0) {
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        int row = (reg & 3) + 8 * (reg >> 2) + 4 * lhalf;
-        float v = acc[t][reg] + red[quad][row][lrow];
-        slab[((int64_t)t * p.C + c0 + qc * 32 + row) * p.K + k0 +
-             qk * 32 + lrow] = v;
-      }
-    }
-  }
+  wgrad2_combine_store<NT>(acc, (float(*)[32][32])X,
+                           dwT + (int64_t)split_id * NT * p.C * p.K, p.C,
+                           p.K, c0, k0, wid, lane);
 #undef CHUNK_INFO
 #undef G_LOAD
 #undef G_WRITE
@@ -795,127 +726,61 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad2_s2_kernel(
 #undef X_DECODE
 }
 
-// chunk geometry of a (Ho, Wo) output, shared by launcher and nslab
-static void wgrad2_s2_geom(int N, int Ho, int Wo, int* rb, int* gb) {
-  if (Wo <= 8) { *rb = 8; *gb = 2; }
-  else if (Wo <= 16) { *rb = 8; *gb = 1; }
-  else { *rb = 4; *gb = 1; }
+// THE (WP, RB, GB) table of conv_wgrad2_s2_kernel: calls f(BwdClass) for
+// the padded-width class of a Wo-wide output.
+template <class F>
+static int wgrad2_s2_class(int Wo, F f) {
+  if (Wo <= 8) return f(BwdClass<8, 8, 2>{});
+  if (Wo <= 16) return f(BwdClass<16, 8, 1>{});
+  return f(BwdClass<32, 4, 1>{});
 }
 
-// split (= slab count) mirrored for the host-side dwT allocation
+// chunking and m-split of a shape in class G.  The launcher and the
+// host-side slab count both take p.split from HERE: the kernel writes
+// exactly the slabs the caller allocated.
+template <class G>
+static Wgrad2S2Params wgrad2_s2_params(G, int N, int H, int W, int C,
+                                       int K) {
+  Wgrad2S2Params p;
+  p.N = N; p.H = H; p.W = W; p.C = C; p.K = K;
+  p.Ho = (H + 1) / 2; p.Wo = (W + 1) / 2;
+  p.nh_rows = N * H;
+  p.bands_per_image = (p.Ho + G::RB - 1) / G::RB;
+  p.total_slots = N * p.bands_per_image;
+  p.total_chunks = (p.total_slots + G::GB - 1) / G::GB;
+  // LDS admits ONE 512-thread block per CU: m-split so the grid is about
+  // one block per CU
+  int grid_ck = (C / WS2_BC) * (K / WS2_BK);
+  p.split = bd_min((256 + grid_ck - 1) / grid_ck, p.total_chunks);
+  return p;
+}
+
+// slab count (= split) for the host-side dwT allocation
 extern "C" int bdbnn_wgrad2_s2_nslab(int N, int H, int W, int C, int K,
                                      int ks) {
   if (!s2_shape_ok(H, W, C, K, ks)) return -1;
-  int Ho = (H + 1) / 2, Wo = (W + 1) / 2, rb, gbn;
-  wgrad2_s2_geom(N, Ho, Wo, &rb, &gbn);
-  int slots = N * ((Ho + rb - 1) / rb);
-  int total_chunks = (slots + gbn - 1) / gbn;
-  int grid_ck = (C / WS2_BC) * (K / WS2_BK);
-  int split = (256 + grid_ck - 1) / grid_ck;
-  return split < total_chunks ? split : total_chunks;
+  return wgrad2_s2_class((W + 1) / 2, [&](auto cls) {
+    return wgrad2_s2_params(cls, N, H, W, C, K).split;
+  });
 }
 
 extern "C" int bdbnn_conv_wgrad2_s2(const void* g, const uint64_t* planes,
                                     float* dwT, int ks, int N, int H, int W,
                                     int C, int K, hipStream_t stream) {
   if (!s2_shape_ok(H, W, C, K, ks)) return -1;
-  Wgrad2S2Params p;
-  p.N = N; p.H = H; p.W = W; p.C = C; p.K = K;
-  p.Ho = (H + 1) / 2; p.Wo = (W + 1) / 2;
-  p.nh_rows = N * H;
-  int grid_ck = (C / WS2_BC) * (K / WS2_BK);
-  // LDS admits ONE 512-thread block per CU: m-split so the grid is about
-  // one block per CU
-  p.split = (256 + grid_ck - 1) / grid_ck;
-#define WLAUNCH(WPV, RBV, GBV, KSV)                                       \
-  {                                                                       \
-    p.bands_per_image = (p.Ho + (RBV)-1) / (RBV);                         \
-    p.total_slots = N * p.bands_per_image;                                \
-    p.total_chunks = (p.total_slots + (GBV)-1) / (GBV);                   \
-    if (p.split > p.total_chunks) p.split = p.total_chunks;               \
-    dim3 grid(grid_ck * p.split);                                         \
-    conv_wgrad2_s2_kernel<WPV, RBV, GBV, KSV><<<grid, 512, 0, stream>>>(  \
-        (const __bf16*)g, planes, dwT, p, grid_ck);                       \
-    return 0;                                                             \
-  }
-#define WCLASS(KSV)                                                       \
-  {                                                                       \
-    if (p.Wo <= 8) WLAUNCH(8, 8, 2, KSV)                                  \
-    else if (p.Wo <= 16) WLAUNCH(16, 8, 1, KSV)                           \
-    else WLAUNCH(32, 4, 1, KSV)                                           \
-  }
-  if (ks == 3) WCLASS(3)
-  WCLASS(1)
-#undef WCLASS
-#undef WLAUNCH
-}
-
-// ---------------- parity c-plane repack ----------------
-// xp [N*H*W][CW] (bit c of word = sign of x[p, 32cw+c])  ->  planes u64
-// [C][N*H]: one word per (c, image row); bit r = column 2r (even
-// columns), bit 32+r = column 2r+1 (odd columns).  Row parity is the
-// row index's, so the four parity planes are the two halves of the even
-// and of the odd rows.
-__global__ void repack_cplane_s2_kernel(const uint32_t* __restrict__ xp,
-                                        uint64_t* __restrict__ planes,
-                                        int NH, int W, int C, int CW) {
-  // one thread per (c-word cw, image row): builds 32 u64 rows bit by bit
-  GRID_STRIDE(i, (int64_t)NH * CW) {
-    int cw = int(i % CW);
-    int64_t row = i / CW;
-    const uint32_t* src = xp + (row * W) * CW + cw;
-    uint64_t acc[32];
-#pragma unroll
-    for (int c = 0; c < 32; ++c) acc[c] = 0;
-    for (int x = 0; x < W; ++x) {
-      uint32_t word = src[(int64_t)x * CW];
-      int pos = (x >> 1) + ((x & 1) << 5);
-#pragma unroll
-      for (int c = 0; c < 32; ++c)
-        acc[c] |= (uint64_t)((word >> c) & 1) << pos;
-    }
-#pragma unroll
-    for (int c = 0; c < 32; ++c) {
-      int cc = cw * 32 + c;
-      if (cc < C) planes[(int64_t)cc * NH + row] = acc[c];
-    }
-  }
-}
-
-extern "C" void bdbnn_repack_cplane_s2(const uint32_t* xp, uint64_t* planes,
-                                       int NH, int W, int C, int CW,
-                                       hipStream_t stream) {
-  int64_t total = (int64_t)NH * CW;
-  int blocks = (int)bd_min<int64_t>((total + 255) / 256, 8192);
-  repack_cplane_s2_kernel<<<blocks, 256, 0, stream>>>(xp, planes, NH, W, C,
-                                                      CW);
-}
-
-// ---------------- wgrad finish: slab sum + transpose + STE mask ----
-// dw[k][c][t] = sum_s dwT[s][t][c][k] * 1(|w[k][c][t]| <= 1), T = ks*ks
-__global__ void wgrad_finish_s2_kernel(const float* __restrict__ dwT,
-                                       const float* __restrict__ w,
-                                       float* __restrict__ dw, int C, int K,
-                                       int T, int nslab) {
-  int64_t stride = (int64_t)T * C * K;
-  GRID_STRIDE(i, stride) {
-    int t = int(i % T);
-    int64_t rem = i / T;
-    int c = int(rem % C);
-    int k = int(rem / C);
-    float wv = w[i];
-    int64_t j = ((int64_t)t * C + c) * K + k;
-    float v = 0.f;
-    for (int s = 0; s < nslab; ++s) v += dwT[s * stride + j];
-    dw[i] = (wv <= 1.f && wv >= -1.f) ? v : 0.f;
-  }
-}
-
-extern "C" void bdbnn_wgrad_finish_s2(const float* dwT, const float* w,
-                                      float* dw, int C, int K, int T,
-                                      int nslab, hipStream_t stream) {
-  int64_t total = (int64_t)T * C * K;
-  int blocks = (int)bd_min<int64_t>((total + 255) / 256, 8192);
-  wgrad_finish_s2_kernel<<<blocks, 256, 0, stream>>>(dwT, w, dw, C, K, T,
-                                                     nslab);
+  return wgrad2_s2_class((W + 1) / 2, [&](auto cls) {
+    using G = decltype(cls);
+    Wgrad2S2Params p = wgrad2_s2_params(cls, N, H, W, C, K);
+    int grid_ck = (C / WS2_BC) * (K / WS2_BK);
+    dim3 grid(grid_ck * p.split);
+    if (ks == 3)
+      conv_wgrad2_s2_kernel<G::WP, G::RB, G::GB, 3>
+          <<<grid, 512, 0, stream>>>((const __bf16*)g, planes, dwT, p,
+                                     grid_ck);
+    else
+      conv_wgrad2_s2_kernel<G::WP, G::RB, G::GB, 1>
+          <<<grid, 512, 0, stream>>>((const __bf16*)g, planes, dwT, p,
+                                     grid_ck);
+    return 0;
+  });
 }

@@ -56,16 +56,8 @@ __global__ __launch_bounds__(256) void xnor_conv_kernel(
     const float* __restrict__ alpha, const float* __restrict__ stab,
     TO* __restrict__ out, float* __restrict__ s1, float* __restrict__ s2,
     XnorConvParams p, int grid_m) {
-  // XCD-aware block remap (8 XCDs, private L2s): give each XCD a
-  // contiguous run of spatial tiles so neighbouring tiles (sharing input
-  // rows) land on one L2.  bijective for any grid size.
-  int nwg = gridDim.x;
-  int wg = blockIdx.x;
-  {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, idx = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  // XCD-aware block remap: each XCD gets a contiguous run of spatial tiles
+  const int wg = bd_xcd_remap(blockIdx.x, gridDim.x);
   int m_blk = wg % grid_m;        // spatial tile
   int k_blk = wg / grid_m;        // channel tile
   const int tid = threadIdx.x;

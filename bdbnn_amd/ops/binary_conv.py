@@ -58,29 +58,90 @@ def _act_grad_mask(x: torch.Tensor, mode: str, t, k) -> torch.Tensor:
     return (x.abs() <= 1).to(x.dtype)
 
 
-def _use_s2(nat, g, x_dtype, w, stride, padding, H, W, C):
-    """Route a stride-2 conv's backward to the owned parity kernels?
-    (H, W) is the INPUT size; the native predicate decides the shape."""
-    K, kh, kw = w.shape[0], w.shape[2], w.shape[3]
-    return (_MFMA_BWD and _MFMA_BWD_S2 and g.dtype == torch.bfloat16
-            and x_dtype == torch.bfloat16 and stride == 2 and kh == kw
-            and (kh, padding) in ((3, 1), (1, 0))
-            and nat.dgrad2_s2_supported(H, W, C, K, kh))
+def _owned_route(nat, *, g_dtype, x_dtype, stride, padding, ks, H_in, W_in,
+                 H_out, W_out, C, K, mask_mode, valmask):
+    """Which owned MFMA backward runs a binary conv: "s1" (3x3/s1/p1,
+    csrc/conv_bwd.hip), "s2" (3x3/s2/p1 and 1x1/s2/p0, csrc/conv_bwd_s2.hip)
+    or None (MIOpen on decoded operands).  The whole routing decision:
+    knobs, dtypes, geometry, and the native shape predicates.  ks is the
+    (square) kernel size; a value-mask context that carries the clip-STE
+    mask (mask_mode 0) has no owned kernel."""
+    if not _MFMA_BWD or (valmask and mask_mode == 0):
+        return None
+    if g_dtype != torch.bfloat16 or x_dtype != torch.bfloat16:
+        return None
+    if (ks, stride, padding) == (3, 1, 1):
+        return "s1" if nat.dgrad2_supported(H_out, W_out, C, K) else None
+    if _MFMA_BWD_S2 and stride == 2 and (ks, padding) in ((3, 1), (1, 0)):
+        return "s2" if nat.dgrad2_s2_supported(H_in, W_in, C, K, ks) else None
+    return None
 
 
-def _s2_backward(nat, g, w, xp, wp, alpha, C, H, W, mode, mp, x, t, k, acc):
-    """Owned stride-2 backward: parity-phase dgrad with the mask (and the
-    deferred skip grad, if any) in its epilogue, wgrad from the sign bits
-    repacked by column parity — no decoded activation, no mask pass."""
-    kh = w.shape[2]
-    g = g.contiguous(memory_format=torch.channels_last)
-    wd = (nat.dgrad_weight_decode(wp, alpha, C) if kh == 3
-          else nat.dgrad_weight_decode_1x1(wp, alpha, C))
-    dx = nat.conv_dgrad2_s2(g, wd, H, W, C, mode, mp, x, t, k, acc)
-    planes = nat.repack_cplane_s2(xp, C, H, W)
-    dwT = nat.conv_wgrad2_s2(g, planes, C, H, W, kh)
-    dw = nat.wgrad_finish_s2(dwT, w.float())
+def _owned_backward(nat, route, g, w, xp, wp, alpha, C, mode, mp, x, t, k,
+                    acc):
+    """The owned backward of either route and either mask kind (mode 0:
+    bitplane mp; 1/2: value mask of the saved activation x).  dgrad: halo
+    (s1) / parity-phase (s2) implicit GEMM with the mask and the deferred
+    skip grad, if any, in its epilogue.  wgrad: all-tap block GEMM straight
+    from the sign BITS, repacked per channel (the dense +-1 activation is
+    never materialized), then slab sum + transpose + |w|<=1 mask in one
+    pass."""
+    s2 = route == "s2"
+    H, W, ks = xp.shape[1], xp.shape[2], w.shape[2]
+    wd = (nat.dgrad_weight_decode_1x1 if ks == 1
+          else nat.dgrad_weight_decode)(wp, alpha, C)
+    if s2:
+        dx = nat.conv_dgrad2_s2(g, wd, H, W, C, mode, mp, x, t, k, acc)
+        planes = nat.repack_cplane_s2(xp, C, H, W)
+        dwT = nat.conv_wgrad2_s2(g, planes, C, H, W, ks)
+        dw = nat.wgrad_finish_s2(dwT, w.float())
+    else:
+        dx = (nat.conv_dgrad2(g, wd, mp, C, acc) if mode == 0
+              else nat.conv_dgrad2_x(g, wd, x, C, mode, t, k, acc))
+        planes = nat.repack_cplane(xp, C, W)
+        dwT = nat.conv_wgrad2(g, planes, C)
+        dw = nat.wgrad_finish(dwT, w.float())
     return dx, dw
+
+
+def _conv_backward(g, xb, wb, stride, padding):
+    return torch.ops.aten.convolution_backward(
+        g, xb, wb, None, [stride, stride], [padding, padding], [1, 1], False,
+        [0, 0], 1, [True, True, False])[:2]
+
+
+def _packed_fallback(nat, g, w, xp, mp, wp, alpha, C, x_dtype, stride,
+                     padding):
+    """MIOpen on operands decoded from the bit planes, separate mask
+    kernels; g is channels_last."""
+    bf16 = g.dtype == torch.bfloat16
+    xb = nat.decode_packed(xp, C, bf16)
+    wb = nat.weight_decode(wp, alpha, C, bf16)
+    dxb, dwb = _conv_backward(g, xb, wb, stride, padding)
+    dx = nat.mask_mul_packed(dxb, mp, C, x_dtype == torch.bfloat16)
+    return dx, nat.ste_mask_mul(dwb, w, 0, 0.0, 0.0)
+
+
+def _value_fallback(g, x, w, stride, padding, act_mode, t, k):
+    """Dense conv on +-1 operands decoded from the saved activation, then
+    the activation-gradient mask of x: native kernels on the GPU (g is
+    channels_last there), the pure-torch oracle on the CPU."""
+    if not x.is_cuda:
+        dxb, dwb = _conv_backward(g, binsign(x), weight_scale(w) * binsign(w),
+                                  stride, padding)
+        return (dxb * _act_grad_mask(x, act_mode, t, k),
+                dwb * (w.abs() <= 1).to(w.dtype))
+    nat = _C.native_required()
+    # decode +-1 operands in the compute dtype for the dense MFMA pass
+    xb = nat.binsign_decode(x, 1 if g.dtype == torch.bfloat16 else 0)
+    wb = (weight_scale(w) * binsign(w)).to(g.dtype)
+    dxb, dwb = _conv_backward(g, xb, wb, stride, padding)
+    if t is not None and k is not None:
+        mode_id, t, k = 2, float(t), float(k)
+    else:
+        mode_id, t, k = {"ste": 0, "approx": 1}[act_mode], 0.0, 0.0
+    return (nat.ste_mask_mul(dxb, x, mode_id, t, k),
+            nat.ste_mask_mul(dwb, w, 0, 0.0, 0.0))
 
 
 class BinaryConvFunction(torch.autograd.Function):
@@ -178,114 +239,41 @@ class BinaryConvFunction(torch.autograd.Function):
     def backward(ctx, g, _gs1=None, _gs2=None):
         stride, padding = ctx.stride, ctx.padding
         acc = ctx.skip_cell.pop("g", None) if ctx.skip_cell else None
-        if ctx.packed:
-            w, xp, mp, wp, alpha = ctx.saved_tensors
+        if ctx.packed or ctx.valmask:
             nat = _C.native_required()
-            bf16 = g.dtype == torch.bfloat16
-            C = ctx.in_channels
-            K, kh = w.shape[0], w.shape[2]
+            if ctx.packed:
+                w, xp, mp, wp, alpha = ctx.saved_tensors
+                x, x_dtype, C = None, ctx.x_dtype, ctx.in_channels
+                mode, t, k = 0, 0.0, 0.0
+            else:
+                w, xp, x, wp, alpha = ctx.saved_tensors
+                mp, x_dtype, C = None, x.dtype, x.shape[1]
+                mode, t, k = ctx.mask_mode, ctx.mask_t, ctx.mask_k
             g = g.contiguous(memory_format=torch.channels_last)
-            H, W = g.shape[2], g.shape[3]
-            # hand-written MFMA dgrad (halo implicit GEMM, clip-STE mask
-            # fused into the epilogue) — the default on the hot path
-            use2 = (_MFMA_BWD and bf16 and ctx.x_dtype == torch.bfloat16
-                    and stride == 1 and padding == 1 and kh == 3
-                    and nat.dgrad2_supported(H, W, C, K))
-            if use2:
-                # dgrad: halo implicit GEMM, clip-STE mask (+ deferred
-                # skip grad, if any) fused into the epilogue
-                wd = nat.dgrad_weight_decode(wp, alpha, C)
-                dx = nat.conv_dgrad2(g, wd, mp, C, acc)
-                # wgrad: all-9-tap block GEMM straight from the sign
-                # BITS (the dense +-1 activation tensor is never
-                # materialized), then transpose + |w|<=1 mask in one pass
-                xcp = nat.repack_cplane(xp, C, W)
-                dwT = nat.conv_wgrad2(g, xcp, C)
-                dw = nat.wgrad_finish(dwT, w.float())
-                return (dx, dw.to(w.dtype), None, None, None, None, None,
-                        None, None, None, None)
-            if _use_s2(nat, g, ctx.x_dtype, w, stride, padding,
-                       xp.shape[1], xp.shape[2], C):
-                dx, dw = _s2_backward(nat, g, w, xp, wp, alpha, C,
-                                      xp.shape[1], xp.shape[2], 0, mp, None,
-                                      0.0, 0.0, acc)
-                return (dx, dw.to(w.dtype), None, None, None, None, None,
-                        None, None, None, None)
-            xb = nat.decode_packed(xp, C, bf16)
-            wb = nat.weight_decode(wp, alpha, C, bf16)
-            dxb, dwb = torch.ops.aten.convolution_backward(
-                g, xb, wb, None,
-                [stride, stride], [padding, padding], [1, 1], False, [0, 0],
-                1, [True, True, False])[:2]
-            dx = nat.mask_mul_packed(dxb, mp, C,
-                                     ctx.x_dtype == torch.bfloat16)
-            if acc is not None:
-                dx = dx + acc.to(dx.dtype)
-            dw = nat.ste_mask_mul(dwb, w, 0, 0.0, 0.0)
-            return (dx, dw.to(w.dtype), None, None, None, None, None,
-                    None, None, None, None)
-        if ctx.valmask:
-            w, xp, x, wp, alpha = ctx.saved_tensors
-            nat = _C.native_required()
-            C, K, kh = x.shape[1], w.shape[0], w.shape[2]
-            H, W = g.shape[2], g.shape[3]
-            # same hand-written MFMA kernels as the clip-STE path; the
-            # dgrad epilogue evaluates the ReAct / EDE mask from x
-            use2 = (_MFMA_BWD and ctx.mask_mode != 0
-                    and g.dtype == torch.bfloat16
-                    and x.dtype == torch.bfloat16
-                    and stride == 1 and padding == 1 and kh == 3
-                    and nat.dgrad2_supported(H, W, C, K))
-            if use2:
-                g = g.contiguous(memory_format=torch.channels_last)
-                wd = nat.dgrad_weight_decode(wp, alpha, C)
-                dx = nat.conv_dgrad2_x(g, wd, x, C, ctx.mask_mode,
-                                       ctx.mask_t, ctx.mask_k, acc)
-                xcp = nat.repack_cplane(xp, C, W)
-                dwT = nat.conv_wgrad2(g, xcp, C)
-                dw = nat.wgrad_finish(dwT, w.float())
-                return (dx, dw.to(w.dtype), None, None, None, None, None,
-                        None, None, None, None)
-            if ctx.mask_mode != 0 and _use_s2(
-                    nat, g, x.dtype, w, stride, padding, x.shape[2],
-                    x.shape[3], C):
-                dx, dw = _s2_backward(nat, g, w, xp, wp, alpha, C,
-                                      x.shape[2], x.shape[3], ctx.mask_mode,
-                                      None, x, ctx.mask_t, ctx.mask_k, acc)
-                return (dx, dw.to(w.dtype), None, None, None, None, None,
-                        None, None, None, None)
+            route = _owned_route(
+                nat, g_dtype=g.dtype, x_dtype=x_dtype, stride=stride,
+                padding=padding,
+                ks=w.shape[2] if w.shape[2] == w.shape[3] else 0,
+                H_in=xp.shape[1], W_in=xp.shape[2], H_out=g.shape[2],
+                W_out=g.shape[3], C=C, K=w.shape[0], mask_mode=mode,
+                valmask=ctx.valmask)
+            if route:
+                dx, dw = _owned_backward(nat, route, g, w, xp, wp, alpha, C,
+                                         mode, mp, x, t, k, acc)
+                acc = None  # added in the dgrad epilogue
+            elif ctx.packed:
+                dx, dw = _packed_fallback(nat, g, w, xp, mp, wp, alpha, C,
+                                          x_dtype, stride, padding)
+            else:
+                dx, dw = _value_fallback(g, x, w, stride, padding,
+                                         ctx.act_mode, ctx.t, ctx.k)
         else:
             x, w = ctx.saved_tensors
-        if x.is_cuda:
-            nat = _C.native_required()
-            # decode +-1 operands in the compute dtype for the dense MFMA pass
-            cdt = torch.bfloat16 if g.dtype == torch.bfloat16 else g.dtype
-            xb = nat.binsign_decode(x, 1 if cdt == torch.bfloat16 else 0)
-            wb = (weight_scale(w) * binsign(w)).to(cdt)
-        else:
-            xb = binsign(x)
-            wb = weight_scale(w) * binsign(w)
-        g = g.contiguous(memory_format=torch.channels_last) if g.is_cuda else g
-        dxb, dwb = torch.ops.aten.convolution_backward(
-            g, xb, wb, None,
-            [stride, stride], [padding, padding], [1, 1], False, [0, 0], 1,
-            [True, True, False])[:2]
-        if x.is_cuda:
-            nat = _C.native_required()
-            mode_id = {"ste": 0, "approx": 1}[ctx.act_mode]
-            if ctx.t is not None and ctx.k is not None:
-                mode_id, t, k = 2, float(ctx.t), float(ctx.k)
-            else:
-                t, k = 0.0, 0.0
-            dx = nat.ste_mask_mul(dxb, x, mode_id, t, k)
-            dw = nat.ste_mask_mul(dwb, w, 0, 0.0, 0.0)
-        else:
-            dx = dxb * _act_grad_mask(x, ctx.act_mode, ctx.t, ctx.k)
-            dw = dwb * (w.abs() <= 1).to(w.dtype)
+            dx, dw = _value_fallback(g, x, w, stride, padding, ctx.act_mode,
+                                     ctx.t, ctx.k)
         if acc is not None:
             dx = dx + acc.to(dx.dtype)
-        return (dx, dw.to(w.dtype), None, None, None, None, None, None,
-                None, None, None)
+        return (dx, dw.to(w.dtype)) + (None,) * 9
 
 
 class _HardBinaryConvBase(nn.Module):
