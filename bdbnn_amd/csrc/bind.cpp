@@ -108,6 +108,23 @@ void bdbnn_bn_act_bwd_apply(const void*, const void*, const void*,
 void bdbnn_bn_act_eval(const void*, const void*, const float*, const float*,
                        const float*, const float*, const float*, void*,
                        int64_t, int, int, float, bool, hipStream_t);
+void bdbnn_bn_relu_maxpool_fwd(const void*, const float*, const float*,
+                               const float*, const float*, void*,
+                               unsigned char*, uint32_t*, uint32_t*, int,
+                               int, int, int, int, int, int, int, int, bool,
+                               hipStream_t);
+void bdbnn_bn_relu_maxpool_bwd_reduce(const void*, const unsigned char*,
+                                      const void*, const float*,
+                                      const float*, const float*,
+                                      const float*, float*, float*, int,
+                                      int, int, int, int, int, int, int,
+                                      int, bool, hipStream_t);
+void bdbnn_bn_relu_maxpool_bwd_apply(const void*, const unsigned char*,
+                                     const void*, const float*,
+                                     const float*, const float*,
+                                     const float*, const float*, void*, int,
+                                     int, int, int, int, int, int, int, int,
+                                     bool, hipStream_t);
 void bdbnn_kurtosis_fwd(const TensorListArg*, const int*, const int64_t*,
                         int, double*, const float*, float*, float*, float*,
                         hipStream_t);
@@ -706,6 +723,175 @@ at::Tensor bn_act_eval(const at::Tensor& x,
   return out;
 }
 
+// ---------------- fused stem tail: BN + ReLU + maxpool (csrc/bn_pool.hip) --
+
+// window and channel checks shared by the two entry points; sets Ho, Wo
+static void check_bn_pool_geom(const at::Tensor& x, int64_t ks,
+                               int64_t stride, int64_t pad, int64_t& Ho,
+                               int64_t& Wo, const char* who) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
+                  (x.scalar_type() == at::kBFloat16 ||
+                   x.scalar_type() == at::kFloat),
+              who, ": x must be a 4-D bf16 or fp32 CUDA tensor");
+  int64_t C = x.size(1);
+  TORCH_CHECK(C >= 8 && C <= 1024 && (C & (C - 1)) == 0, who,
+              ": C must be a power of two, 8 <= C <= 1024");
+  TORCH_CHECK(ks >= 1 && ks <= 15 && stride >= 1 && pad >= 0 &&
+                  2 * pad <= ks,
+              who, ": need 1 <= ks <= 15 (u8 tap index), stride >= 1, "
+              "0 <= pad <= ks/2");
+  Ho = (x.size(2) + 2 * pad - ks) / stride + 1;
+  Wo = (x.size(3) + 2 * pad - ks) / stride + 1;
+  TORCH_CHECK(x.size(2) + 2 * pad >= ks && x.size(3) + 2 * pad >= ks &&
+                  Ho >= 1 && Wo >= 1,
+              who, ": window larger than the padded input");
+  TORCH_CHECK(x.size(0) * x.size(2) * x.size(3) < (int64_t(1) << 31), who,
+              ": N*H*W must be < 2^31");
+}
+
+static void check_chan_f32(const at::Tensor& t, int64_t C, const char* name,
+                           const char* who) {
+  TORCH_CHECK(t.is_cuda() && t.numel() == C, who, ": ", name,
+              " must be a CUDA tensor of C elements");
+}
+
+std::vector<at::Tensor> bn_relu_maxpool_fwd_train(
+    const at::Tensor& x, const at::Tensor& gamma, const at::Tensor& beta,
+    c10::optional<at::Tensor> running_mean,
+    c10::optional<at::Tensor> running_var, double momentum, double eps,
+    int64_t ks, int64_t stride, int64_t pad,
+    const c10::optional<at::Tensor>& pre_s1,
+    const c10::optional<at::Tensor>& pre_s2, bool want_pack) {
+  const char* who = "bn_relu_maxpool_fwd_train";
+  int64_t Ho, Wo;
+  check_bn_pool_geom(x, ks, stride, pad, Ho, Wo, who);
+  auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
+  int N = (int)x.size(0), C = (int)x.size(1);
+  int H = (int)x.size(2), W = (int)x.size(3);
+  check_chan_f32(gamma, C, "gamma", who);
+  check_chan_f32(beta, C, "beta", who);
+  TORCH_CHECK(pre_s1.has_value() == pre_s2.has_value(), who,
+              ": pre_s1 and pre_s2 go together");
+  int64_t n = xc.numel();
+  bool bf16 = is_bf16(xc);
+  auto fopt = xc.options().dtype(at::kFloat);
+  at::Tensor s1, s2;
+  int nslice = 1;
+  auto mean = at::empty({C}, fopt);
+  auto invstd = at::empty({C}, fopt);
+  if (pre_s1.has_value()) {
+    // pre-accumulated statistics, possibly [nslice][C] partial sums
+    s1 = pre_s1->contiguous();
+    s2 = pre_s2->contiguous();
+    TORCH_CHECK(s1.is_cuda() && s2.is_cuda() &&
+                    s1.scalar_type() == at::kFloat &&
+                    s2.scalar_type() == at::kFloat &&
+                    s1.numel() == s2.numel(),
+                who, ": stats must be matching fp32 CUDA tensors");
+    nslice = (int)(s1.numel() / C);
+    TORCH_CHECK(nslice >= 1 && (int64_t)nslice * C == s1.numel(), who,
+                ": stats shape mismatch");
+  } else {
+    s1 = at::empty({32, C}, fopt);   // sliced partials (finalize folds)
+    s2 = at::empty({32, C}, fopt);
+    nslice = 32;
+    bdbnn_bn_stats(xc.data_ptr(), s1.data_ptr<float>(),
+                   s2.data_ptr<float>(), n, C, bf16, cur_stream());
+  }
+  float *rm = nullptr, *rv = nullptr;
+  if (running_mean.has_value()) {
+    TORCH_CHECK(running_var.has_value() &&
+                    running_mean->scalar_type() == at::kFloat &&
+                    running_var->scalar_type() == at::kFloat &&
+                    running_mean->is_contiguous() &&
+                    running_var->is_contiguous() &&
+                    running_mean->numel() == C && running_var->numel() == C,
+                who, ": running stats must be contiguous fp32 [C]");
+    rm = running_mean->data_ptr<float>();
+    rv = running_var->data_ptr<float>();
+  }
+  bdbnn_bn_finalize(s1.data_ptr<float>(), s2.data_ptr<float>(),
+                    mean.data_ptr<float>(), invstd.data_ptr<float>(), rm, rv,
+                    C, (float)(n / C), (float)momentum, (float)eps, nslice,
+                    cur_stream());
+  auto gf = gamma.contiguous().to(at::kFloat);
+  auto bf = beta.contiguous().to(at::kFloat);
+  auto out = at::empty({N, C, Ho, Wo}, xc.options(),
+                       at::MemoryFormat::ChannelsLast);
+  auto idx = at::empty({N, Ho, Wo, C}, xc.options().dtype(at::kByte));
+  at::Tensor xpk, mpk;
+  uint32_t *xpk_p = nullptr, *mpk_p = nullptr;
+  if (want_pack) {
+    TORCH_CHECK(C % 32 == 0, who, ": pack fusion needs C % 32 == 0");
+    auto iopt = xc.options().dtype(at::kInt);
+    xpk = at::empty({N, Ho, Wo, C / 32}, iopt);
+    mpk = at::empty({N, Ho, Wo, C / 32}, iopt);
+    xpk_p = (uint32_t*)xpk.data_ptr<int>();
+    mpk_p = (uint32_t*)mpk.data_ptr<int>();
+  }
+  bdbnn_bn_relu_maxpool_fwd(xc.data_ptr(), mean.data_ptr<float>(),
+                            invstd.data_ptr<float>(), gf.data_ptr<float>(),
+                            bf.data_ptr<float>(), out.data_ptr(),
+                            idx.data_ptr<unsigned char>(), xpk_p, mpk_p, N,
+                            C, H, W, (int)Ho, (int)Wo, (int)ks, (int)stride,
+                            (int)pad, bf16, cur_stream());
+  if (want_pack) return {out, idx, mean, invstd, xpk, mpk};
+  return {out, idx, mean, invstd};
+}
+
+std::vector<at::Tensor> bn_relu_maxpool_bwd(
+    const at::Tensor& dy, const at::Tensor& idx, const at::Tensor& x,
+    const at::Tensor& mean, const at::Tensor& invstd,
+    const at::Tensor& gamma, const at::Tensor& beta, int64_t ks,
+    int64_t stride, int64_t pad) {
+  const char* who = "bn_relu_maxpool_bwd";
+  int64_t Ho, Wo;
+  check_bn_pool_geom(x, ks, stride, pad, Ho, Wo, who);
+  auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
+  int N = (int)x.size(0), C = (int)x.size(1);
+  int H = (int)x.size(2), W = (int)x.size(3);
+  TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 && dy.size(0) == N &&
+                  dy.size(1) == C && dy.size(2) == Ho && dy.size(3) == Wo,
+              who, ": dy must be the pooled shape (N,C,Ho,Wo)");
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == at::kByte &&
+                  idx.is_contiguous() && idx.dim() == 4 &&
+                  idx.size(0) == N && idx.size(1) == Ho &&
+                  idx.size(2) == Wo && idx.size(3) == C,
+              who, ": idx must be contiguous u8 [N][Ho][Wo][C]");
+  check_chan_f32(gamma, C, "gamma", who);
+  check_chan_f32(beta, C, "beta", who);
+  TORCH_CHECK(mean.is_cuda() && invstd.is_cuda() &&
+                  mean.scalar_type() == at::kFloat &&
+                  invstd.scalar_type() == at::kFloat &&
+                  mean.is_contiguous() && invstd.is_contiguous() &&
+                  mean.numel() == C && invstd.numel() == C,
+              who, ": mean and invstd must be contiguous fp32 [C]");
+  auto dyc =
+      dy.to(xc.scalar_type()).contiguous(at::MemoryFormat::ChannelsLast);
+  bool bf16 = is_bf16(xc);
+  auto fopt = xc.options().dtype(at::kFloat);
+  auto gf = gamma.contiguous().to(at::kFloat);
+  auto bf = beta.contiguous().to(at::kFloat);
+  auto sums32 = at::empty({32, C, 2}, fopt);  // sliced partials
+  auto sums = at::empty({C, 2}, fopt);
+  bdbnn_bn_relu_maxpool_bwd_reduce(
+      dyc.data_ptr(), idx.data_ptr<unsigned char>(), xc.data_ptr(),
+      mean.data_ptr<float>(), invstd.data_ptr<float>(),
+      gf.data_ptr<float>(), bf.data_ptr<float>(), sums32.data_ptr<float>(),
+      sums.data_ptr<float>(), N, C, H, W, (int)Ho, (int)Wo, (int)ks,
+      (int)stride, (int)pad, bf16, cur_stream());
+  auto dx = at::empty_like(xc, xc.options(), at::MemoryFormat::ChannelsLast);
+  bdbnn_bn_relu_maxpool_bwd_apply(
+      dyc.data_ptr(), idx.data_ptr<unsigned char>(), xc.data_ptr(),
+      mean.data_ptr<float>(), invstd.data_ptr<float>(),
+      gf.data_ptr<float>(), bf.data_ptr<float>(), sums.data_ptr<float>(),
+      dx.data_ptr(), N, C, H, W, (int)Ho, (int)Wo, (int)ks, (int)stride,
+      (int)pad, bf16, cur_stream());
+  auto dbeta = sums.select(1, 0).clone();
+  auto dgamma = sums.select(1, 1).clone();
+  return {dx, dgamma, dbeta};
+}
+
 // ---------------- MFMA backward (csrc/conv_bwd.hip, conv_bwd_s2.hip) -----
 // Argument handling shared by the stride-1 and stride-2 entry points;
 // `who` is the python-visible name, for the message.
@@ -1216,6 +1402,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused BN(+add)(+act) training forward");
   m.def("bn_act_bwd", &bn_act_bwd, "fused BN(+add)(+act) backward");
   m.def("bn_act_eval", &bn_act_eval, "fused BN(+add)(+act) eval forward");
+  m.def("bn_relu_maxpool_fwd_train", &bn_relu_maxpool_fwd_train,
+        "fused BN + ReLU + maxpool training forward -> [out, idx, mean, "
+        "invstd(, xpk, mpk)]",
+        py::arg("x"), py::arg("gamma"), py::arg("beta"),
+        py::arg("running_mean"), py::arg("running_var"),
+        py::arg("momentum"), py::arg("eps"), py::arg("ks"),
+        py::arg("stride"), py::arg("pad"), py::arg("pre_s1") = py::none(),
+        py::arg("pre_s2") = py::none(), py::arg("want_pack") = false);
+  m.def("bn_relu_maxpool_bwd", &bn_relu_maxpool_bwd,
+        "fused BN + ReLU + maxpool backward -> [dx, dgamma, dbeta]");
   m.def("conv_dgrad2", &conv_dgrad2,
         "MFMA bf16 dgrad v2: halo-staged 9-tap implicit GEMM with fused "
         "clip-STE mask (3x3/s1/p1); optional acc adds a same-shape "

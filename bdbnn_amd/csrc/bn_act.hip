@@ -17,6 +17,7 @@
 // act_kind: 0 = identity, 1 = per-channel PReLU, 2 = ReLU.
 #include "common.h"
 #include "vec8.h"
+#include "bn_affine.h"
 
 // ---- pass 1: per-channel sum / sumsq ----
 template <typename T>
@@ -122,11 +123,10 @@ __global__ void bn_act_fwd_kernel(const T* __restrict__ x,
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     int cc = m.c0 + j;
-    sc[j] = gamma[cc] * invstd[cc];
-    sh[j] = beta[cc] - mean[cc] * sc[j];
+    bn_scale_shift(gamma[cc], beta[cc], mean[cc], invstd[cc], sc[j], sh[j]);
     av[j] = (ACT == 1) ? a[cc] : 0.f;
   }
-  const int sub = threadIdx.x & 3;         // byte slot within the word
+  const int sub = threadIdx.x & 3;       // byte slot within the word
   const int64_t cw = m.c0 >> 5;            // word column (lane sub == 0)
   const int CW = C >> 5;
   float v[8], s[8], z[8], o[8];
@@ -136,11 +136,11 @@ __global__ void bn_act_fwd_kernel(const T* __restrict__ x,
     if (skip != nullptr) load8(skip, i, s);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      z[j] = sc[j] * v[j] + sh[j];
+      z[j] = bn_affine(sc[j], v[j], sh[j]);
       if (skip != nullptr) z[j] += s[j];
       o[j] = z[j];
       if (ACT == 1) o[j] = z[j] > 0.f ? z[j] : av[j] * z[j];
-      else if (ACT == 2) o[j] = fmaxf(z[j], 0.f);
+      else if (ACT == 2) o[j] = bn_relu(z[j]);
     }
     store8(out, i, o);
     if (zout != nullptr) store8(zout, i, z);
@@ -507,6 +507,12 @@ extern "C" void bdbnn_bn_act_bwd_reduce(const void* dy, const void* z,
                              act_kind, grid, lds, stream);
   bn_fold_sums_kernel<<<(C * 3 + 255) / 256, 256, 0, stream>>>(sums32, sums,
                                                                C * 3);
+}
+
+// the slice fold on its own, for csrc/bn_pool.hip's reduce
+extern "C" void bdbnn_bn_fold_sums(const float* sums32, float* sums, int n,
+                                   hipStream_t stream) {
+  bn_fold_sums_kernel<<<(n + 255) / 256, 256, 0, stream>>>(sums32, sums, n);
 }
 
 extern "C" void bdbnn_bn_act_bwd_apply(const void* dy, const void* z,

@@ -26,7 +26,7 @@ from ..ops.binary_conv import HardBinaryConv
 from ..ops.stem_conv import StemConv7x7
 from ..ops.binarize import LearnableBias
 from ..ops.activations import ChannelPReLU
-from ..ops.bn_act import fused_bn_act
+from ..ops.bn_act import fused_bn_act, fused_bn_relu_maxpool
 from ..ops.pool import FusedMaxPool2d
 
 
@@ -34,6 +34,12 @@ from ..ops.pool import FusedMaxPool2d
 # epilogue (kills autograd's separate dx+dskip accumulation pass,
 # ~3.3 ms/step at b2048); see ops/bn_act.py / ops/binary_conv.py
 _FUSE_SKIP_GRAD = os.environ.get("BDBNN_FUSE_SKIP_GRAD", "1") == "1"
+
+# run the ImageNet stem tail bn1 -> ReLU -> maxpool as one fused op in
+# training (csrc/bn_pool.hip: no full-resolution ReLU output, no
+# full-resolution pool gradient, layer1.0.conv1's pack in the epilogue);
+# BDBNN_FUSE_STEM_POOL=0 keeps the bn_act + maxpool composition for A/B
+_FUSE_STEM_POOL = os.environ.get("BDBNN_FUSE_STEM_POOL", "1") == "1"
 
 
 class FusedDownsample(nn.Sequential):
@@ -198,7 +204,16 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.maxpool(fused_bn_act(self.conv1(x), self.bn1, "relu"))
+        x = self.conv1(x)
+        if _FUSE_STEM_POOL and isinstance(self.maxpool, FusedMaxPool2d):
+            # binary models: layer1.0 takes its conv1's bitplanes with x
+            # (BiBasicBlock accepts the tuple); real blocks take x alone
+            x = fused_bn_relu_maxpool(x, self.bn1, self.maxpool,
+                                      pack=self.binary)
+            if self.binary and x[1] is None:
+                x = x[0]
+        else:
+            x = self.maxpool(fused_bn_act(x, self.bn1, "relu"))
         x = self.layer1(x)
         x = self.layer2(x)
         x = self.layer3(x)

@@ -17,6 +17,7 @@ import torch.nn.functional as F
 
 from .. import _C
 from .activations import ChannelPReLU
+from .pool import FusedMaxPool2d
 
 _ACT_NONE, _ACT_PRELU, _ACT_RELU = 0, 1, 2
 
@@ -66,6 +67,69 @@ class _BNActFn(torch.autograd.Function):
                 da if ctx.has_a else None,
                 None, None, None, None, None, None, None, None, None,
                 None)
+
+
+class _BNReluPoolFn(torch.autograd.Function):
+    """bn -> ReLU -> maxpool as one op (csrc/bn_pool.hip).  Neither the
+    ReLU output nor the pool's input gradient is materialised: forward
+    saves the BN input x and the u8 argmax plane, backward recomputes the
+    ReLU mask from x and gathers dy through the argmax plane."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum,
+                eps, ks, stride, pad, want_pack):
+        nat = _C.native_required()
+        res = nat.bn_relu_maxpool_fwd_train(
+            x, gamma, beta, running_mean, running_var, momentum, eps,
+            ks, stride, pad, None, None, want_pack)
+        out, idx, mean, invstd = res[:4]
+        ctx.save_for_backward(x, idx, mean, invstd, gamma, beta)
+        ctx.pool = (ks, stride, pad)
+        if want_pack:
+            xpk, mpk = res[4], res[5]
+            ctx.mark_non_differentiable(xpk, mpk)
+            return out, xpk, mpk
+        dummy = out.new_empty(0)
+        ctx.mark_non_differentiable(dummy)
+        return out, dummy, dummy
+
+    @staticmethod
+    def backward(ctx, dy, _gxpk=None, _gmpk=None):
+        x, idx, mean, invstd, gamma, beta = ctx.saved_tensors
+        ks, stride, pad = ctx.pool
+        dx, dgamma, dbeta = _C.native_required().bn_relu_maxpool_bwd(
+            dy, idx, x, mean, invstd, gamma, beta, ks, stride, pad)
+        return (dx, dgamma, dbeta, None, None, None, None, None, None,
+                None, None)
+
+
+def fused_bn_relu_maxpool(x, bn: nn.BatchNorm2d, pool, pack=False):
+    """pool(relu(bn(x))) — the ImageNet stem tail.
+
+    One fused op when bn is training with grad enabled, x is a CUDA 4-D
+    tensor with C a power of two in [8, 1024], and pool is a
+    FusedMaxPool2d; every other case (eval, no_grad, CPU, any other pool
+    module) is the composition ``pool(fused_bn_act(x, bn, "relu"))``.
+
+    pack=True: returns (out, (xp, mp) | None) like fused_bn_act — the
+    consuming binary conv's bitplanes of the pooled output, produced only
+    by the fused path with C % 32 == 0."""
+    C = x.size(1) if x.dim() == 4 else 0
+    if (bn.training and torch.is_grad_enabled() and x.is_cuda
+            and x.dim() == 4 and 8 <= C <= 1024 and (C & (C - 1)) == 0
+            and isinstance(pool, FusedMaxPool2d) and _C.has_native()):
+        if bn.track_running_stats and bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+        want_pack = bool(pack) and C % 32 == 0
+        out, xpk, mpk = _BNReluPoolFn.apply(
+            x, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+            bn.momentum if bn.momentum is not None else 0.1, bn.eps,
+            pool.kernel_size, pool.stride, pool.padding, want_pack)
+        if pack:
+            return out, ((xpk, mpk) if want_pack else None)
+        return out
+    out = pool(fused_bn_act(x, bn, "relu"))
+    return (out, None) if pack else out
 
 
 def fused_bn_act(x, bn: nn.BatchNorm2d, act=None, skip=None, stats=None,

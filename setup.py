@@ -23,6 +23,7 @@ sources = [os.path.join(CSRC, f) for f in (
     "pack.hip",
     "prelu.hip",
     "bn_act.hip",
+    "bn_pool.hip",
     "pool.hip",
     "loss.hip",
     "conv_dgrad.hip",
