@@ -154,6 +154,24 @@ hipStream_t cur_stream() {
 
 bool is_bf16(const at::Tensor& t) { return t.scalar_type() == at::kBFloat16; }
 
+// Argument check of the elementwise kernels that pick `bf16 ? bf16 : float`
+// from the tensor: any other dtype would be read as float, past the end
+// of an fp16 buffer.  vec8_c: the tensor is also indexed by chan_map8
+// (csrc/vec8.h), one thread per 8 channels, which needs a 4-D tensor with
+// C a power of two in [8, 1024] (C < 8 divides by zero threads per row).
+void check_vec8(const at::Tensor& t, bool vec8_c, const char* name,
+                const char* who) {
+  TORCH_CHECK(t.is_cuda() && (t.scalar_type() == at::kBFloat16 ||
+                              t.scalar_type() == at::kFloat),
+              who, ": ", name, " must be a bf16 or fp32 CUDA tensor");
+  if (vec8_c) {
+    TORCH_CHECK(t.dim() == 4, who, ": ", name, " must be 4-D (N,C,H,W)");
+    int64_t C = t.size(1);
+    TORCH_CHECK(C >= 8 && C <= 1024 && (C & (C - 1)) == 0, who,
+                ": C must be a power of two, 8 <= C <= 1024");
+  }
+}
+
 // Build the multi-tensor block schedule (block -> tensor, offset) on the
 // device.  chunk_elems must match the kernels' CHUNK_ELEMS.
 struct Schedule {
@@ -236,6 +254,7 @@ PtrList make_ptrs(const std::vector<at::Tensor>& ts) {
 
 at::Tensor sign_pack_nhwc(const at::Tensor& x) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4, "sign_pack: 4-D CUDA tensor");
+  check_vec8(x, false, "x", "sign_pack");
   TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
               "sign_pack: channels_last input required");
   int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
@@ -263,7 +282,7 @@ std::vector<at::Tensor> weight_pack(const at::Tensor& w) {
 }
 
 at::Tensor binsign_decode(const at::Tensor& x, bool out_bf16) {
-  TORCH_CHECK(x.is_cuda(), "binsign_decode: CUDA tensor");
+  check_vec8(x, false, "x", "binsign_decode");
   TORCH_CHECK(x.numel() % 8 == 0, "binsign_decode: numel % 8 == 0");
   auto fmt = x.dim() == 4 ? at::MemoryFormat::ChannelsLast
                           : at::MemoryFormat::Contiguous;
@@ -279,6 +298,8 @@ at::Tensor ste_mask_mul(const at::Tensor& g, const at::Tensor& x, int mode,
                         double t, double k) {
   TORCH_CHECK(g.is_cuda() && x.is_cuda() && g.numel() == x.numel(),
               "ste_mask_mul: matching CUDA tensors");
+  check_vec8(g, false, "g", "ste_mask_mul");
+  check_vec8(x, false, "x", "ste_mask_mul");
   TORCH_CHECK(x.numel() % 8 == 0, "ste_mask_mul: numel % 8 == 0");
   auto fmt = x.dim() == 4 ? at::MemoryFormat::ChannelsLast
                           : at::MemoryFormat::Contiguous;
@@ -295,6 +316,7 @@ at::Tensor ste_mask_mul(const at::Tensor& g, const at::Tensor& x, int mode,
 
 std::vector<at::Tensor> sign_mask_pack_nhwc(const at::Tensor& x) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4, "sign_mask_pack: 4-D CUDA tensor");
+  check_vec8(x, false, "x", "sign_mask_pack");
   TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
               "sign_mask_pack: channels_last input required");
   int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
@@ -324,6 +346,7 @@ at::Tensor decode_packed(const at::Tensor& sp, int64_t C, bool out_bf16) {
 at::Tensor mask_mul_packed(const at::Tensor& g, const at::Tensor& mp,
                            int64_t C, bool out_bf16) {
   TORCH_CHECK(g.is_cuda() && mp.is_cuda(), "mask_mul_packed: CUDA tensors");
+  check_vec8(g, false, "g", "mask_mul_packed");
   auto gc = g.contiguous(at::MemoryFormat::ChannelsLast);
   int64_t N = mp.size(0), H = mp.size(1), W = mp.size(2);
   int CW = (int)mp.size(3);
@@ -499,6 +522,7 @@ at::Tensor ce_bwd(const at::Tensor& s, const at::Tensor& y,
 std::vector<at::Tensor> maxpool_fwd(const at::Tensor& x, int64_t ks,
                                     int64_t stride, int64_t pad) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4, "maxpool_fwd: 4-D CUDA tensor");
+  check_vec8(x, false, "x", "maxpool_fwd");
   auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
   int N = (int)x.size(0), C = (int)x.size(1);
   int H = (int)x.size(2), W = (int)x.size(3);
@@ -517,6 +541,8 @@ std::vector<at::Tensor> maxpool_fwd(const at::Tensor& x, int64_t ks,
 at::Tensor maxpool_bwd(const at::Tensor& dy, const at::Tensor& idx,
                        int64_t H, int64_t W, int64_t ks, int64_t stride,
                        int64_t pad) {
+  TORCH_CHECK(dy.dim() == 4, "maxpool_bwd: 4-D CUDA tensor");
+  check_vec8(dy, false, "dy", "maxpool_bwd");
   auto dyc = dy.contiguous(at::MemoryFormat::ChannelsLast);
   int N = (int)dy.size(0), C = (int)dy.size(1);
   int Ho = (int)dy.size(2), Wo = (int)dy.size(3);
@@ -531,11 +557,12 @@ at::Tensor maxpool_bwd(const at::Tensor& dy, const at::Tensor& idx,
 // ---------------- prelu ----------------
 
 at::Tensor prelu_fwd(const at::Tensor& x, const at::Tensor& a) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4, "prelu_fwd: 4-D CUDA tensor");
+  check_vec8(x, true, "x", "prelu_fwd");
+  int C = (int)x.size(1);
+  TORCH_CHECK(a.is_cuda() && a.numel() == C,
+              "prelu_fwd: a must be a CUDA tensor of C elements");
   auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
   auto af = a.contiguous().to(at::kFloat);
-  int C = (int)x.size(1);
-  TORCH_CHECK(C <= 1024, "prelu: C <= 1024");
   auto y = at::empty_like(xc, xc.options(), at::MemoryFormat::ChannelsLast);
   bdbnn_prelu_fwd(xc.data_ptr(), af.data_ptr<float>(), y.data_ptr(),
                   xc.numel(), C, xc.scalar_type() == at::kBFloat16,
@@ -545,12 +572,16 @@ at::Tensor prelu_fwd(const at::Tensor& x, const at::Tensor& a) {
 
 std::vector<at::Tensor> prelu_bwd(const at::Tensor& g, const at::Tensor& x,
                                   const at::Tensor& a) {
+  check_vec8(x, true, "x", "prelu_bwd");
+  check_vec8(g, true, "g", "prelu_bwd");
+  TORCH_CHECK(g.scalar_type() == x.scalar_type() && g.sizes() == x.sizes(),
+              "prelu_bwd: grad dtype and shape must match input");
+  int C = (int)x.size(1);
+  TORCH_CHECK(a.is_cuda() && a.numel() == C,
+              "prelu_bwd: a must be a CUDA tensor of C elements");
   auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
   auto gc = g.contiguous(at::MemoryFormat::ChannelsLast);
-  TORCH_CHECK(gc.scalar_type() == xc.scalar_type(),
-              "prelu_bwd: grad dtype must match input");
   auto af = a.contiguous().to(at::kFloat);
-  int C = (int)x.size(1);
   auto dx = at::empty_like(xc, xc.options(), at::MemoryFormat::ChannelsLast);
   auto da = at::empty({C}, xc.options().dtype(at::kFloat));
   bdbnn_prelu_bwd(xc.data_ptr(), gc.data_ptr(), af.data_ptr<float>(),
@@ -569,9 +600,14 @@ std::vector<at::Tensor> bn_act_fwd_train(
     c10::optional<at::Tensor> running_var, double momentum, double eps,
     int64_t act_kind, const c10::optional<at::Tensor>& pre_s1,
     const c10::optional<at::Tensor>& pre_s2, bool want_pack) {
+  check_vec8(x, true, "x", "bn_act_fwd_train");
   auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
   int C = (int)x.size(1);
-  TORCH_CHECK(C <= 1024, "fused bn: C <= 1024");
+  TORCH_CHECK(gamma.numel() == C && beta.numel() == C &&
+                  (!a.has_value() || a->numel() == C),
+              "bn_act_fwd_train: gamma, beta and a must have C elements");
+  TORCH_CHECK(act_kind != 1 || a.has_value(),
+              "bn_act_fwd_train: PReLU needs its slopes a");
   int64_t n = xc.numel();
   bool bf16 = is_bf16(xc);
   auto fopt = xc.options().dtype(at::kFloat);
@@ -582,10 +618,17 @@ std::vector<at::Tensor> bn_act_fwd_train(
   if (pre_s1.has_value()) {
     // stats already accumulated by the producing conv's epilogue
     // (possibly as [nslice][C] partial sums — finalize folds them)
-    s1 = *pre_s1;
-    s2 = *pre_s2;
+    TORCH_CHECK(pre_s2.has_value(), "bn: pre_s1 and pre_s2 go together");
+    s1 = pre_s1->contiguous();
+    s2 = pre_s2->contiguous();
+    TORCH_CHECK(s1.is_cuda() && s2.is_cuda() &&
+                    s1.scalar_type() == at::kFloat &&
+                    s2.scalar_type() == at::kFloat &&
+                    s1.numel() == s2.numel(),
+                "bn: stats must be matching fp32 CUDA tensors");
     nslice = (int)(s1.numel() / C);
-    TORCH_CHECK(nslice * C == s1.numel(), "bn: stats shape mismatch");
+    TORCH_CHECK(nslice >= 1 && (int64_t)nslice * C == s1.numel(),
+                "bn: stats shape mismatch");
   } else {
     s1 = at::empty({32, C}, fopt);   // sliced partials (finalize folds)
     s2 = at::empty({32, C}, fopt);
@@ -651,6 +694,19 @@ std::vector<at::Tensor> bn_act_bwd(
     const at::Tensor& mean, const at::Tensor& invstd,
     const at::Tensor& gamma, const c10::optional<at::Tensor>& a,
     int64_t act_kind, bool need_dskip) {
+  check_vec8(x, true, "x", "bn_act_bwd");
+  check_vec8(dy, true, "dy", "bn_act_bwd");
+  TORCH_CHECK(dy.sizes() == x.sizes(), "bn_act_bwd: dy shape must match x");
+  // identity never reads z; the other kinds read it with x's type and index
+  TORCH_CHECK(act_kind == 0 || (z.is_cuda() && z.sizes() == x.sizes() &&
+                                z.scalar_type() == x.scalar_type()),
+              "bn_act_bwd: z must match x in shape and dtype");
+  TORCH_CHECK(mean.numel() == x.size(1) && invstd.numel() == x.size(1) &&
+                  gamma.numel() == x.size(1) &&
+                  (!a.has_value() || a->numel() == x.size(1)),
+              "bn_act_bwd: mean, invstd, gamma and a must have C elements");
+  TORCH_CHECK(act_kind != 1 || a.has_value(),
+              "bn_act_bwd: PReLU needs its slopes a");
   auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
   auto zc = z.contiguous(at::MemoryFormat::ChannelsLast);
   auto dyc = dy.to(xc.scalar_type()).contiguous(at::MemoryFormat::ChannelsLast);
@@ -696,6 +752,13 @@ at::Tensor bn_act_eval(const at::Tensor& x,
                        const c10::optional<at::Tensor>& a,
                        const at::Tensor& rm, const at::Tensor& rv,
                        double eps, int64_t act_kind) {
+  check_vec8(x, true, "x", "bn_act_eval");
+  TORCH_CHECK(gamma.numel() == x.size(1) && beta.numel() == x.size(1) &&
+                  rm.numel() == x.size(1) && rv.numel() == x.size(1) &&
+                  (!a.has_value() || a->numel() == x.size(1)),
+              "bn_act_eval: per-channel tensors must have C elements");
+  TORCH_CHECK(act_kind != 1 || a.has_value(),
+              "bn_act_eval: PReLU needs its slopes a");
   auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
   int C = (int)x.size(1);
   int64_t n = xc.numel();

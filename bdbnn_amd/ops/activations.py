@@ -11,14 +11,13 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _C
+from ._vec8 import tensor_vec8_supported
 
 
 class _ChannelPReLUFn(torch.autograd.Function):
     @staticmethod
     def _fused_ok(x):
-        C = x.size(1)
-        return (x.is_cuda and x.dim() == 4 and C <= 1024
-                and (C & (C - 1)) == 0)
+        return tensor_vec8_supported(x)
 
     @staticmethod
     def forward(ctx, x, w):

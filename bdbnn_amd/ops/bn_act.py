@@ -8,7 +8,8 @@ activation (profiles/r01_bench_b256_kernel_stats.md).  Parameters stay
 in the ordinary ``nn.BatchNorm2d`` / ``ChannelPReLU`` modules, so
 checkpoints are unchanged.
 
-CPU (and any non-channels_last corner): exact composition fallback.
+CPU (and any tensor ops/_vec8.py rules out: not 4-D, C not a power of two
+in [8, 1024], dtype other than fp32 / bf16): exact composition fallback.
 """
 
 import torch
@@ -16,6 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _C
+from ._vec8 import tensor_vec8_supported
 from .activations import ChannelPReLU
 from .pool import FusedMaxPool2d
 
@@ -114,10 +116,9 @@ def fused_bn_relu_maxpool(x, bn: nn.BatchNorm2d, pool, pack=False):
     pack=True: returns (out, (xp, mp) | None) like fused_bn_act — the
     consuming binary conv's bitplanes of the pooled output, produced only
     by the fused path with C % 32 == 0."""
-    C = x.size(1) if x.dim() == 4 else 0
-    if (bn.training and torch.is_grad_enabled() and x.is_cuda
-            and x.dim() == 4 and 8 <= C <= 1024 and (C & (C - 1)) == 0
+    if (bn.training and torch.is_grad_enabled() and tensor_vec8_supported(x)
             and isinstance(pool, FusedMaxPool2d) and _C.has_native()):
+        C = x.size(1)
         if bn.track_running_stats and bn.num_batches_tracked is not None:
             bn.num_batches_tracked.add_(1)
         want_pack = bool(pack) and C % 32 == 0
@@ -155,9 +156,8 @@ def fused_bn_act(x, bn: nn.BatchNorm2d, act=None, skip=None, stats=None,
         out = act(out)
         return (out, None) if pack else out
 
-    C = x.size(1) if x.dim() == 4 else 0
-    use_fused = (x.is_cuda and x.dim() == 4 and 0 < C <= 1024
-                 and (C & (C - 1)) == 0 and _C.has_native())
+    use_fused = tensor_vec8_supported(x) and _C.has_native()
+    C = x.size(1) if use_fused else 0
     if use_fused and bn.training:
         if bn.track_running_stats and bn.num_batches_tracked is not None:
             bn.num_batches_tracked.add_(1)

@@ -6,6 +6,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _C
+from ._vec8 import tensor_vec8_supported
 
 
 class _MaxPoolFn(torch.autograd.Function):
@@ -38,9 +39,7 @@ class FusedMaxPool2d(nn.Module):
         self.padding = padding
 
     def forward(self, x):
-        C = x.size(1) if x.dim() == 4 else 0
-        if (x.is_cuda and x.dim() == 4 and 8 <= C <= 1024
-                and (C & (C - 1)) == 0 and _C.has_native()):
+        if tensor_vec8_supported(x) and _C.has_native():
             return _MaxPoolFn.apply(x, self.kernel_size, self.stride,
                                     self.padding)
         return F.max_pool2d(x, self.kernel_size, self.stride, self.padding)
