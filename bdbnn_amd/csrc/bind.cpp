@@ -7,144 +7,10 @@
 
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
-// ---- mirrors of csrc/common.h (kept in sync) ----
-constexpr int BDBNN_MAX_TENSORS = 64;
-struct TensorListArg {
-  const float* ptr[BDBNN_MAX_TENSORS];
-  int64_t numel[BDBNN_MAX_TENSORS];
-  int n;
-};
-struct PtrList { float* ptr[BDBNN_MAX_TENSORS]; };
-
-extern "C" {
-void bdbnn_sign_pack(const void*, uint32_t*, int64_t, int, int, bool,
-                     hipStream_t);
-void bdbnn_binsign_decode(const void*, void*, int64_t, bool, bool,
-                          hipStream_t);
-void bdbnn_ste_mask_mul(const void*, const void*, void*, int64_t, bool, bool,
-                        int, float, float, hipStream_t);
-void bdbnn_weight_pack(const float*, uint32_t*, float*, float*, int, int,
-                       int, int, int, hipStream_t);
-void bdbnn_xnor_conv_fwd(const uint32_t*, const uint32_t*, const float*,
-                         const float*, void*, float*, float*, bool, int,
-                         int, int, int, int, int, int, int, int, int, int,
-                         hipStream_t);
-void bdbnn_sign_mask_pack(const void*, uint32_t*, uint32_t*, int64_t, int,
-                          int, bool, hipStream_t);
-void bdbnn_decode_packed(const uint32_t*, void*, int64_t, int, int, bool,
-                         hipStream_t);
-void bdbnn_mask_mul_packed(const void*, const uint32_t*, void*, int64_t,
-                           int, int, bool, bool, hipStream_t);
-void bdbnn_weight_decode(const uint32_t*, const float*, void*, int, int,
-                         int, int, bool, hipStream_t);
-void bdbnn_maxpool_fwd(const void*, void*, unsigned char*, int, int, int,
-                       int, int, int, int, int, int, bool, hipStream_t);
-void bdbnn_maxpool_bwd(const void*, const unsigned char*, void*, int, int,
-                       int, int, int, int, int, int, int, bool,
-                       hipStream_t);
-void bdbnn_kd_logit_fwd(const void*, const void*, float*, float*, int,
-                        int, bool, hipStream_t);
-void bdbnn_kd_logit_bwd(const void*, const void*, const float*, void*,
-                        float, int, int, bool, hipStream_t);
-void bdbnn_ce_fwd(const void*, const int64_t*, float*, float*, int, int,
-                  bool, hipStream_t);
-void bdbnn_ce_bwd(const void*, const int64_t*, const float*, void*, float,
-                  int, int, bool, hipStream_t);
-void bdbnn_conv_dgrad(const void*, const uint32_t*, const float*, void*,
-                      int, int, int, int, int, int, hipStream_t);
-int bdbnn_conv_dgrad2(const void*, const void*, const uint32_t*,
-                      const void*, void*, const void*, int, float, float,
-                      int, int, int, int, int, hipStream_t);
-int bdbnn_dgrad2_supported(int, int, int, int);
-void bdbnn_dgrad_wdec(const uint32_t*, const float*, void*, int, int, int,
-                      hipStream_t);
-int bdbnn_conv_wgrad2(const void*, const uint64_t*, float*, int, int, int,
-                      int, int, hipStream_t);
-int bdbnn_wgrad2_nslab(int, int, int, int, int);
-int bdbnn_dgrad2_s2_supported(int, int, int, int, int);
-int bdbnn_s2_kernels_can_run(int, int, int, int, int);
-int bdbnn_conv_dgrad2_s2(const void*, const void*, const uint32_t*,
-                         const void*, void*, const void*, int, int, float,
-                         float, int, int, int, int, int, hipStream_t);
-int bdbnn_wgrad2_s2_nslab(int, int, int, int, int, int);
-int bdbnn_conv_wgrad2_s2(const void*, const uint64_t*, float*, int, int,
-                         int, int, int, int, hipStream_t);
-void bdbnn_stem_pack_x4(const void*, void*, int64_t, bool, hipStream_t);
-void bdbnn_stem_pack_w4(const float*, void*, hipStream_t);
-void bdbnn_stem_fwd(const void*, const void*, void*, int, int, int,
-                    hipStream_t);
-int bdbnn_stem_wrw_nslab(int, int, int);
-void bdbnn_stem_wrw(const void*, const void*, float*, int, int, int,
-                    hipStream_t);
-void bdbnn_stem_fold_dw4(const float*, float*, int, hipStream_t);
-void bdbnn_repack_cplane(const uint32_t*, uint64_t*, int, int, int, int,
-                         bool, hipStream_t);
-void bdbnn_wgrad_finish(const float*, const float*, float*, int, int, int,
-                        int, hipStream_t);
-void bdbnn_conv_wgrad(const void*, const uint32_t*, float*, int, int, int,
-                      int, int, int, hipStream_t);
-void bdbnn_prelu_fwd(const void*, const float*, void*, int64_t, int, bool,
-                     hipStream_t);
-void bdbnn_prelu_bwd(const void*, const void*, const float*, void*, float*,
-                     int64_t, int, bool, hipStream_t);
-void bdbnn_bn_stats(const void*, float*, float*, int64_t, int, bool,
-                    hipStream_t);
-void bdbnn_bn_finalize(const float*, const float*, float*, float*, float*,
-                       float*, int, float, float, float, int, hipStream_t);
-void bdbnn_bn_act_fwd(const void*, const void*, const float*, const float*,
-                      const float*, const float*, const float*, void*, void*,
-                      int64_t, int, int, uint32_t*, uint32_t*, bool,
-                      hipStream_t);
-void bdbnn_bn_act_bwd_reduce(const void*, const void*, const void*,
-                             const float*, const float*, const float*,
-                             float*, float*, int64_t, int, int, bool,
-                             hipStream_t);
-void bdbnn_bn_act_bwd_apply(const void*, const void*, const void*,
-                            const float*, const float*, const float*,
-                            const float*, const float*, void*, void*,
-                            int64_t, int, int, float, bool, hipStream_t);
-void bdbnn_bn_act_eval(const void*, const void*, const float*, const float*,
-                       const float*, const float*, const float*, void*,
-                       int64_t, int, int, float, bool, hipStream_t);
-void bdbnn_bn_relu_maxpool_fwd(const void*, const float*, const float*,
-                               const float*, const float*, void*,
-                               unsigned char*, uint32_t*, uint32_t*, int,
-                               int, int, int, int, int, int, int, int, bool,
-                               hipStream_t);
-void bdbnn_bn_relu_maxpool_bwd_reduce(const void*, const unsigned char*,
-                                      const void*, const float*,
-                                      const float*, const float*,
-                                      const float*, float*, float*, int,
-                                      int, int, int, int, int, int, int,
-                                      int, bool, hipStream_t);
-void bdbnn_bn_relu_maxpool_bwd_apply(const void*, const unsigned char*,
-                                     const void*, const float*,
-                                     const float*, const float*,
-                                     const float*, const float*, void*, int,
-                                     int, int, int, int, int, int, int, int,
-                                     bool, hipStream_t);
-void bdbnn_kurtosis_fwd(const TensorListArg*, const int*, const int64_t*,
-                        int, double*, const float*, float*, float*, float*,
-                        hipStream_t);
-void bdbnn_kurtosis_bwd(const TensorListArg*, const PtrList*, const int*,
-                        const int64_t*, int, const float*, const float*,
-                        const float*, hipStream_t);
-void bdbnn_weight_kd_fwd(const TensorListArg*, const PtrList*, const PtrList*,
-                         const int*, const int64_t*, int, double*,
-                         hipStream_t);
-void bdbnn_weight_kd_bwd(const TensorListArg*, const PtrList*, const PtrList*,
-                         const int*, const int64_t*, int, const float*,
-                         hipStream_t);
-void bdbnn_fused_sgd(const TensorListArg*, const PtrList*, const PtrList*,
-                     const PtrList*, const int*, const int64_t*, int, float,
-                     float, float, hipStream_t);
-void bdbnn_fused_adam(const TensorListArg*, const PtrList*, const PtrList*,
-                      const PtrList*, const PtrList*, const int*,
-                      const int64_t*, int, float, float, float, float, float,
-                      float, float, hipStream_t);
-}
+#include "api.h"
 
 namespace {
 
@@ -173,7 +39,7 @@ void check_vec8(const at::Tensor& t, bool vec8_c, const char* name,
 }
 
 // Build the multi-tensor block schedule (block -> tensor, offset) on the
-// device.  chunk_elems must match the kernels' CHUNK_ELEMS.
+// device; callers pass BDBNN_CHUNK_ELEMS, what one block covers.
 struct Schedule {
   at::Tensor bt, bo;   // int32 / int64 device tensors
   int n_blocks;
@@ -242,10 +108,104 @@ TensorListArg make_meta(const std::vector<at::Tensor>& ts) {
   return a;
 }
 
-PtrList make_ptrs(const std::vector<at::Tensor>& ts) {
+// A further list of a fused call.  The kernels index it by the leading
+// list's tensor number and element count, so it must pair up with `lead`
+// (the make_meta of the leading list) one to one.
+PtrList make_ptrs(const std::vector<at::Tensor>& ts,
+                  const TensorListArg& lead) {
+  TORCH_CHECK((int)ts.size() == lead.n,
+              "fused multi-tensor ops need lists of equal length");
   PtrList p;
-  for (size_t i = 0; i < ts.size(); ++i) p.ptr[i] = ts[i].data_ptr<float>();
+  for (size_t i = 0; i < ts.size(); ++i) {
+    TORCH_CHECK(ts[i].is_cuda() && ts[i].scalar_type() == at::kFloat &&
+                    (ts[i].is_contiguous() ||
+                     ts[i].is_contiguous(at::MemoryFormat::ChannelsLast)) &&
+                    ts[i].numel() == lead.numel[i],
+                "fused multi-tensor ops need dense fp32 CUDA tensors sized "
+                "like the leading list's");
+    p.ptr[i] = ts[i].data_ptr<float>();
+  }
   return p;
+}
+
+// fp32 contiguous copy of a per-channel tensor (a no-op for fp32 [C])
+at::Tensor chan_f32(const at::Tensor& t) {
+  return t.contiguous().to(at::kFloat);
+}
+
+// Optional per-channel tensor as the kernels take it: `hold` keeps the
+// fp32 copy alive until the launch is queued; nullptr when absent.
+const float* opt_chan_ptr(const c10::optional<at::Tensor>& t,
+                          at::Tensor& hold) {
+  if (!t.has_value()) return nullptr;
+  hold = chan_f32(*t);
+  return hold.data_ptr<float>();
+}
+
+// Optional skip tensor in xc's dtype, channels_last; same holder rule.
+const void* opt_skip_ptr(const c10::optional<at::Tensor>& skip,
+                         const at::Tensor& xc, at::Tensor& hold) {
+  if (!skip.has_value()) return nullptr;
+  hold = skip->to(xc.scalar_type())
+             .contiguous(at::MemoryFormat::ChannelsLast);
+  return hold.data_ptr();
+}
+
+// a per-channel tensor the kernels read or write through float* as it is
+bool is_f32_chan(const at::Tensor& t, int64_t C) {
+  return t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() &&
+         t.numel() == C;
+}
+
+// Training statistics of the fused BN entry points: {mean, invstd} of xc
+// (channels_last, C channels) from the pre-accumulated sums (possibly
+// [nslice][C] partials of a producing conv's epilogue; finalize folds
+// them) or from a bn_stats pass; updates the running stats when given.
+std::pair<at::Tensor, at::Tensor> bn_train_stats(
+    const at::Tensor& xc, int C, const c10::optional<at::Tensor>& pre_s1,
+    const c10::optional<at::Tensor>& pre_s2,
+    const c10::optional<at::Tensor>& running_mean,
+    const c10::optional<at::Tensor>& running_var, double momentum,
+    double eps, const char* who) {
+  TORCH_CHECK(pre_s1.has_value() == pre_s2.has_value(), who,
+              ": pre_s1 and pre_s2 go together");
+  TORCH_CHECK(running_mean.has_value() == running_var.has_value(), who,
+              ": running_mean and running_var go together");
+  TORCH_CHECK(!running_mean.has_value() ||
+                  (is_f32_chan(*running_mean, C) &&
+                   is_f32_chan(*running_var, C)),
+              who, ": running stats must be contiguous fp32 [C]");
+  int64_t n = xc.numel();
+  auto fopt = xc.options().dtype(at::kFloat);
+  at::Tensor s1, s2;
+  int nslice = 32;
+  if (pre_s1.has_value()) {
+    s1 = pre_s1->contiguous();
+    s2 = pre_s2->contiguous();
+    TORCH_CHECK(s1.is_cuda() && s2.is_cuda() &&
+                    s1.scalar_type() == at::kFloat &&
+                    s2.scalar_type() == at::kFloat &&
+                    s1.numel() == s2.numel(),
+                who, ": stats must be matching fp32 CUDA tensors");
+    nslice = (int)(s1.numel() / C);
+    TORCH_CHECK(nslice >= 1 && (int64_t)nslice * C == s1.numel(), who,
+                ": stats shape mismatch");
+  } else {
+    s1 = at::empty({32, C}, fopt);   // sliced partials (finalize folds)
+    s2 = at::empty({32, C}, fopt);
+    bdbnn_bn_stats(xc.data_ptr(), s1.data_ptr<float>(),
+                   s2.data_ptr<float>(), n, C, is_bf16(xc), cur_stream());
+  }
+  auto mean = at::empty({C}, fopt);
+  auto invstd = at::empty({C}, fopt);
+  bool run = running_mean.has_value();
+  bdbnn_bn_finalize(s1.data_ptr<float>(), s2.data_ptr<float>(),
+                    mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                    run ? running_mean->data_ptr<float>() : nullptr,
+                    run ? running_var->data_ptr<float>() : nullptr, C,
+                    (float)(n / C), (float)momentum, (float)eps, nslice,
+                    cur_stream());
+  return {mean, invstd};
 }
 
 }  // namespace
@@ -562,7 +522,7 @@ at::Tensor prelu_fwd(const at::Tensor& x, const at::Tensor& a) {
   TORCH_CHECK(a.is_cuda() && a.numel() == C,
               "prelu_fwd: a must be a CUDA tensor of C elements");
   auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
-  auto af = a.contiguous().to(at::kFloat);
+  auto af = chan_f32(a);
   auto y = at::empty_like(xc, xc.options(), at::MemoryFormat::ChannelsLast);
   bdbnn_prelu_fwd(xc.data_ptr(), af.data_ptr<float>(), y.data_ptr(),
                   xc.numel(), C, xc.scalar_type() == at::kBFloat16,
@@ -581,7 +541,7 @@ std::vector<at::Tensor> prelu_bwd(const at::Tensor& g, const at::Tensor& x,
               "prelu_bwd: a must be a CUDA tensor of C elements");
   auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
   auto gc = g.contiguous(at::MemoryFormat::ChannelsLast);
-  auto af = a.contiguous().to(at::kFloat);
+  auto af = chan_f32(a);
   auto dx = at::empty_like(xc, xc.options(), at::MemoryFormat::ChannelsLast);
   auto da = at::empty({C}, xc.options().dtype(at::kFloat));
   bdbnn_prelu_bwd(xc.data_ptr(), gc.data_ptr(), af.data_ptr<float>(),
@@ -610,40 +570,9 @@ std::vector<at::Tensor> bn_act_fwd_train(
               "bn_act_fwd_train: PReLU needs its slopes a");
   int64_t n = xc.numel();
   bool bf16 = is_bf16(xc);
-  auto fopt = xc.options().dtype(at::kFloat);
-  at::Tensor s1, s2;
-  int nslice = 1;
-  auto mean = at::empty({C}, fopt);
-  auto invstd = at::empty({C}, fopt);
-  if (pre_s1.has_value()) {
-    // stats already accumulated by the producing conv's epilogue
-    // (possibly as [nslice][C] partial sums — finalize folds them)
-    TORCH_CHECK(pre_s2.has_value(), "bn: pre_s1 and pre_s2 go together");
-    s1 = pre_s1->contiguous();
-    s2 = pre_s2->contiguous();
-    TORCH_CHECK(s1.is_cuda() && s2.is_cuda() &&
-                    s1.scalar_type() == at::kFloat &&
-                    s2.scalar_type() == at::kFloat &&
-                    s1.numel() == s2.numel(),
-                "bn: stats must be matching fp32 CUDA tensors");
-    nslice = (int)(s1.numel() / C);
-    TORCH_CHECK(nslice >= 1 && (int64_t)nslice * C == s1.numel(),
-                "bn: stats shape mismatch");
-  } else {
-    s1 = at::empty({32, C}, fopt);   // sliced partials (finalize folds)
-    s2 = at::empty({32, C}, fopt);
-    nslice = 32;
-    bdbnn_bn_stats(xc.data_ptr(), s1.data_ptr<float>(),
-                   s2.data_ptr<float>(), n, C, bf16, cur_stream());
-  }
-  float* rm = running_mean.has_value()
-                  ? running_mean->data_ptr<float>() : nullptr;
-  float* rv = running_var.has_value()
-                  ? running_var->data_ptr<float>() : nullptr;
-  bdbnn_bn_finalize(s1.data_ptr<float>(), s2.data_ptr<float>(),
-                    mean.data_ptr<float>(), invstd.data_ptr<float>(), rm, rv,
-                    C, (float)(n / C), (float)momentum, (float)eps, nslice,
-                    cur_stream());
+  auto [mean, invstd] =
+      bn_train_stats(xc, C, pre_s1, pre_s2, running_mean, running_var,
+                     momentum, eps, "bn_act_fwd_train");
   auto out = at::empty_like(xc, xc.options(), at::MemoryFormat::ChannelsLast);
   // PReLU backward needs the true pre-activation z; ReLU only needs its
   // sign (recoverable from out) and identity ignores it — skip the write.
@@ -656,18 +585,11 @@ std::vector<at::Tensor> bn_act_fwd_train(
     z = out;
   }
   at::Tensor skipc;
-  const void* skip_ptr = nullptr;
-  if (skip.has_value()) {
-    skipc = skip->to(xc.scalar_type())
-                .contiguous(at::MemoryFormat::ChannelsLast);
-    skip_ptr = skipc.data_ptr();
-  }
-  auto gf = gamma.contiguous().to(at::kFloat);
-  auto bf = beta.contiguous().to(at::kFloat);
+  const void* skip_ptr = opt_skip_ptr(skip, xc, skipc);
+  auto gf = chan_f32(gamma);
+  auto bf = chan_f32(beta);
   at::Tensor af;
-  const float* a_ptr = nullptr;
-  if (a.has_value()) { af = a->contiguous().to(at::kFloat);
-                       a_ptr = af.data_ptr<float>(); }
+  const float* a_ptr = opt_chan_ptr(a, af);
   // consumer-conv sign/mask pack fused into the epilogue (the next
   // binary conv then skips its own pack read pass; csrc/bn_act.hip)
   at::Tensor xpk, mpk;
@@ -717,15 +639,13 @@ std::vector<at::Tensor> bn_act_bwd(
   auto sums32 = at::empty({32, C, 3}, fopt);  // sliced partials
   auto sums = at::empty({C, 3}, fopt);
   at::Tensor af;
-  const float* a_ptr = nullptr;
-  if (a.has_value()) { af = a->contiguous().to(at::kFloat);
-                       a_ptr = af.data_ptr<float>(); }
+  const float* a_ptr = opt_chan_ptr(a, af);
   bdbnn_bn_act_bwd_reduce(dyc.data_ptr(), zc.data_ptr(), xc.data_ptr(),
                           mean.data_ptr<float>(), invstd.data_ptr<float>(),
                           a_ptr, sums32.data_ptr<float>(),
                           sums.data_ptr<float>(), n, C, (int)act_kind,
                           bf16, cur_stream());
-  auto gf = gamma.contiguous().to(at::kFloat);
+  auto gf = chan_f32(gamma);
   auto dx = at::empty_like(xc, xc.options(), at::MemoryFormat::ChannelsLast);
   at::Tensor dskip;
   void* dskip_ptr = nullptr;
@@ -765,20 +685,13 @@ at::Tensor bn_act_eval(const at::Tensor& x,
   bool bf16 = is_bf16(xc);
   auto out = at::empty_like(xc, xc.options(), at::MemoryFormat::ChannelsLast);
   at::Tensor skipc;
-  const void* skip_ptr = nullptr;
-  if (skip.has_value()) {
-    skipc = skip->to(xc.scalar_type())
-                .contiguous(at::MemoryFormat::ChannelsLast);
-    skip_ptr = skipc.data_ptr();
-  }
-  auto gf = gamma.contiguous().to(at::kFloat);
-  auto bf = beta.contiguous().to(at::kFloat);
-  auto rmf = rm.contiguous().to(at::kFloat);
-  auto rvf = rv.contiguous().to(at::kFloat);
+  const void* skip_ptr = opt_skip_ptr(skip, xc, skipc);
+  auto gf = chan_f32(gamma);
+  auto bf = chan_f32(beta);
+  auto rmf = chan_f32(rm);
+  auto rvf = chan_f32(rv);
   at::Tensor af;
-  const float* a_ptr = nullptr;
-  if (a.has_value()) { af = a->contiguous().to(at::kFloat);
-                       a_ptr = af.data_ptr<float>(); }
+  const float* a_ptr = opt_chan_ptr(a, af);
   bdbnn_bn_act_eval(xc.data_ptr(), skip_ptr, rmf.data_ptr<float>(),
                     rvf.data_ptr<float>(), gf.data_ptr<float>(),
                     bf.data_ptr<float>(), a_ptr, out.data_ptr(), n, C,
@@ -792,13 +705,7 @@ at::Tensor bn_act_eval(const at::Tensor& x,
 static void check_bn_pool_geom(const at::Tensor& x, int64_t ks,
                                int64_t stride, int64_t pad, int64_t& Ho,
                                int64_t& Wo, const char* who) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
-                  (x.scalar_type() == at::kBFloat16 ||
-                   x.scalar_type() == at::kFloat),
-              who, ": x must be a 4-D bf16 or fp32 CUDA tensor");
-  int64_t C = x.size(1);
-  TORCH_CHECK(C >= 8 && C <= 1024 && (C & (C - 1)) == 0, who,
-              ": C must be a power of two, 8 <= C <= 1024");
+  check_vec8(x, true, "x", who);
   TORCH_CHECK(ks >= 1 && ks <= 15 && stride >= 1 && pad >= 0 &&
                   2 * pad <= ks,
               who, ": need 1 <= ks <= 15 (u8 tap index), stride >= 1, "
@@ -833,52 +740,11 @@ std::vector<at::Tensor> bn_relu_maxpool_fwd_train(
   int H = (int)x.size(2), W = (int)x.size(3);
   check_chan_f32(gamma, C, "gamma", who);
   check_chan_f32(beta, C, "beta", who);
-  TORCH_CHECK(pre_s1.has_value() == pre_s2.has_value(), who,
-              ": pre_s1 and pre_s2 go together");
-  int64_t n = xc.numel();
   bool bf16 = is_bf16(xc);
-  auto fopt = xc.options().dtype(at::kFloat);
-  at::Tensor s1, s2;
-  int nslice = 1;
-  auto mean = at::empty({C}, fopt);
-  auto invstd = at::empty({C}, fopt);
-  if (pre_s1.has_value()) {
-    // pre-accumulated statistics, possibly [nslice][C] partial sums
-    s1 = pre_s1->contiguous();
-    s2 = pre_s2->contiguous();
-    TORCH_CHECK(s1.is_cuda() && s2.is_cuda() &&
-                    s1.scalar_type() == at::kFloat &&
-                    s2.scalar_type() == at::kFloat &&
-                    s1.numel() == s2.numel(),
-                who, ": stats must be matching fp32 CUDA tensors");
-    nslice = (int)(s1.numel() / C);
-    TORCH_CHECK(nslice >= 1 && (int64_t)nslice * C == s1.numel(), who,
-                ": stats shape mismatch");
-  } else {
-    s1 = at::empty({32, C}, fopt);   // sliced partials (finalize folds)
-    s2 = at::empty({32, C}, fopt);
-    nslice = 32;
-    bdbnn_bn_stats(xc.data_ptr(), s1.data_ptr<float>(),
-                   s2.data_ptr<float>(), n, C, bf16, cur_stream());
-  }
-  float *rm = nullptr, *rv = nullptr;
-  if (running_mean.has_value()) {
-    TORCH_CHECK(running_var.has_value() &&
-                    running_mean->scalar_type() == at::kFloat &&
-                    running_var->scalar_type() == at::kFloat &&
-                    running_mean->is_contiguous() &&
-                    running_var->is_contiguous() &&
-                    running_mean->numel() == C && running_var->numel() == C,
-                who, ": running stats must be contiguous fp32 [C]");
-    rm = running_mean->data_ptr<float>();
-    rv = running_var->data_ptr<float>();
-  }
-  bdbnn_bn_finalize(s1.data_ptr<float>(), s2.data_ptr<float>(),
-                    mean.data_ptr<float>(), invstd.data_ptr<float>(), rm, rv,
-                    C, (float)(n / C), (float)momentum, (float)eps, nslice,
-                    cur_stream());
-  auto gf = gamma.contiguous().to(at::kFloat);
-  auto bf = beta.contiguous().to(at::kFloat);
+  auto [mean, invstd] = bn_train_stats(
+      xc, C, pre_s1, pre_s2, running_mean, running_var, momentum, eps, who);
+  auto gf = chan_f32(gamma);
+  auto bf = chan_f32(beta);
   auto out = at::empty({N, C, Ho, Wo}, xc.options(),
                        at::MemoryFormat::ChannelsLast);
   auto idx = at::empty({N, Ho, Wo, C}, xc.options().dtype(at::kByte));
@@ -923,18 +789,14 @@ std::vector<at::Tensor> bn_relu_maxpool_bwd(
               who, ": idx must be contiguous u8 [N][Ho][Wo][C]");
   check_chan_f32(gamma, C, "gamma", who);
   check_chan_f32(beta, C, "beta", who);
-  TORCH_CHECK(mean.is_cuda() && invstd.is_cuda() &&
-                  mean.scalar_type() == at::kFloat &&
-                  invstd.scalar_type() == at::kFloat &&
-                  mean.is_contiguous() && invstd.is_contiguous() &&
-                  mean.numel() == C && invstd.numel() == C,
-              who, ": mean and invstd must be contiguous fp32 [C]");
+  TORCH_CHECK(is_f32_chan(mean, C) && is_f32_chan(invstd, C), who,
+              ": mean and invstd must be contiguous fp32 [C]");
   auto dyc =
       dy.to(xc.scalar_type()).contiguous(at::MemoryFormat::ChannelsLast);
   bool bf16 = is_bf16(xc);
   auto fopt = xc.options().dtype(at::kFloat);
-  auto gf = gamma.contiguous().to(at::kFloat);
-  auto bf = beta.contiguous().to(at::kFloat);
+  auto gf = chan_f32(gamma);
+  auto bf = chan_f32(beta);
   auto sums32 = at::empty({32, C, 2}, fopt);  // sliced partials
   auto sums = at::empty({C, 2}, fopt);
   bdbnn_bn_relu_maxpool_bwd_reduce(
@@ -1332,7 +1194,7 @@ std::vector<at::Tensor> kurtosis_fwd(const std::vector<at::Tensor>& ws,
                                      const at::Tensor& targets) {
   auto meta = make_meta(ws);
   auto dev = ws[0].device();
-  auto sched = build_schedule(ws, 32 * 1024, dev);
+  auto sched = build_schedule(ws, BDBNN_CHUNK_ELEMS, dev);
   int L = (int)ws.size();
   auto opts = ws[0].options();
   auto mom = at::zeros({L, 4}, opts.dtype(at::kDouble));
@@ -1354,12 +1216,12 @@ std::vector<at::Tensor> kurtosis_bwd(const std::vector<at::Tensor>& ws,
                                      const at::Tensor& gscale) {
   auto meta = make_meta(ws);
   auto dev = ws[0].device();
-  auto sched = build_schedule(ws, 32 * 1024, dev);
+  auto sched = build_schedule(ws, BDBNN_CHUNK_ELEMS, dev);
   std::vector<at::Tensor> grads;
   for (auto& w : ws)  // preserve_format: grad layout == weight layout
     grads.push_back(at::empty_like(w, w.options(),
                                    at::MemoryFormat::Preserve));
-  auto gp = make_ptrs(grads);
+  auto gp = make_ptrs(grads, meta);
   auto tgt = targets.to(dev, at::kFloat).contiguous();
   auto st = stats.contiguous();
   // gscale is a 0-dim DEVICE tensor: no host sync in the backward
@@ -1376,11 +1238,11 @@ std::vector<at::Tensor> kurtosis_bwd(const std::vector<at::Tensor>& ws,
 at::Tensor weight_kd_fwd(const std::vector<at::Tensor>& ws,
                          const std::vector<at::Tensor>& wt) {
   auto meta = make_meta(ws);
-  auto sched = build_schedule(ws, 32 * 1024, ws[0].device());
-  auto s_ptr = make_ptrs(ws);
+  auto sched = build_schedule(ws, BDBNN_CHUNK_ELEMS, ws[0].device());
+  auto s_ptr = make_ptrs(ws, meta);
   std::vector<at::Tensor> wt_c;
   for (auto& t : wt) wt_c.push_back(t.contiguous());
-  auto t_ptr = make_ptrs(wt_c);
+  auto t_ptr = make_ptrs(wt_c, meta);
   auto out = at::zeros({}, ws[0].options().dtype(at::kDouble));
   bdbnn_weight_kd_fwd(&meta, &s_ptr, &t_ptr, sched.bt.data_ptr<int>(),
                       sched.bo.data_ptr<int64_t>(), sched.n_blocks,
@@ -1391,13 +1253,13 @@ at::Tensor weight_kd_fwd(const std::vector<at::Tensor>& ws,
 std::vector<at::Tensor> weight_kd_bwd(const std::vector<at::Tensor>& wt,
                                       const at::Tensor& gscale) {
   auto meta = make_meta(wt);
-  auto sched = build_schedule(wt, 32 * 1024, wt[0].device());
-  auto t_ptr = make_ptrs(wt);
+  auto sched = build_schedule(wt, BDBNN_CHUNK_ELEMS, wt[0].device());
+  auto t_ptr = make_ptrs(wt, meta);
   std::vector<at::Tensor> grads;
   for (auto& t : wt)
     grads.push_back(at::empty_like(t, t.options(),
                                    at::MemoryFormat::Preserve));
-  auto gp = make_ptrs(grads);
+  auto gp = make_ptrs(grads, meta);
   auto gs = gscale.to(wt[0].device(), at::kFloat).contiguous();
   bdbnn_weight_kd_bwd(&meta, &t_ptr, &gp, sched.bt.data_ptr<int>(),
                       sched.bo.data_ptr<int64_t>(), sched.n_blocks,
@@ -1412,10 +1274,10 @@ void fused_sgd(const std::vector<at::Tensor>& p,
                const std::vector<at::Tensor>& buf, double lr, double momentum,
                double wd) {
   auto meta = make_meta(p);
-  auto sched = build_schedule(p, 32 * 1024, p[0].device());
-  auto pp = make_ptrs(p);
-  auto gg = make_ptrs(g);   // python aligns grad layout to the param's
-  auto bb = make_ptrs(buf);
+  auto sched = build_schedule(p, BDBNN_CHUNK_ELEMS, p[0].device());
+  auto pp = make_ptrs(p, meta);
+  auto gg = make_ptrs(g, meta);   // python aligns grad layout to the param's
+  auto bb = make_ptrs(buf, meta);
   bdbnn_fused_sgd(&meta, &pp, &gg, &bb, sched.bt.data_ptr<int>(),
                   sched.bo.data_ptr<int64_t>(), sched.n_blocks, (float)lr,
                   (float)momentum, (float)wd, cur_stream());
@@ -1427,11 +1289,11 @@ void fused_adam(const std::vector<at::Tensor>& p,
                 const std::vector<at::Tensor>& m2, double lr, double beta1,
                 double beta2, double eps, double wd, double bc1, double bc2) {
   auto meta = make_meta(p);
-  auto sched = build_schedule(p, 32 * 1024, p[0].device());
-  auto pp = make_ptrs(p);
-  auto gg = make_ptrs(g);   // python aligns grad layout to the param's
-  auto mm1 = make_ptrs(m1);
-  auto mm2 = make_ptrs(m2);
+  auto sched = build_schedule(p, BDBNN_CHUNK_ELEMS, p[0].device());
+  auto pp = make_ptrs(p, meta);
+  auto gg = make_ptrs(g, meta);   // python aligns grad layout to the param's
+  auto mm1 = make_ptrs(m1, meta);
+  auto mm2 = make_ptrs(m2, meta);
   bdbnn_fused_adam(&meta, &pp, &gg, &mm1, &mm2, sched.bt.data_ptr<int>(),
                    sched.bo.data_ptr<int64_t>(), sched.n_blocks, (float)lr,
                    (float)beta1, (float)beta2, (float)eps, (float)wd,

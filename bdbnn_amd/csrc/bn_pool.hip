@@ -425,8 +425,6 @@ static void launch_pool_fwd(const void* x, const float* mean,
 #undef POOL_FWD
 }
 
-extern "C" void bdbnn_bn_fold_sums(const float*, float*, int, hipStream_t);
-
 extern "C" void bdbnn_bn_relu_maxpool_fwd(
     const void* x, const float* mean, const float* invstd,
     const float* gamma, const float* beta, void* out, unsigned char* idx,

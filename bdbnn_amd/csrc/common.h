@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "api.h"  // launcher prototypes, TensorListArg, PtrList, chunk size
+
 #define BDBNN_WAVE 64
 
 template <typename T>
@@ -37,12 +39,3 @@ __device__ __forceinline__ int bd_xcd_remap(int wg, int nwg) {
 #define GRID_STRIDE(i, n)                                            \
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;   \
        i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-// Multi-tensor descriptor: fits in kernel args (<4 KB).
-constexpr int BDBNN_MAX_TENSORS = 64;
-
-struct TensorListArg {
-  const float* ptr[BDBNN_MAX_TENSORS];
-  int64_t numel[BDBNN_MAX_TENSORS];
-  int n;
-};

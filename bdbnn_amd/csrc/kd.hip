@@ -7,19 +7,15 @@
 // d/dW_s = -exp(W_t)/numel.
 #include "common.h"
 
-struct PtrList2 { float* ptr[BDBNN_MAX_TENSORS]; };
-
-constexpr int64_t KD_CHUNK_ELEMS = 32 * 1024;
-
-__global__ void weight_kd_fwd_kernel(TensorListArg ws_meta, PtrList2 ws,
-                                     PtrList2 wt,
+__global__ void weight_kd_fwd_kernel(TensorListArg ws_meta, PtrList ws,
+                                     PtrList wt,
                                      const int* __restrict__ block_tensor,
                                      const int64_t* __restrict__ block_off,
                                      double* __restrict__ out) {
   int l = block_tensor[blockIdx.x];
   int64_t n = ws_meta.numel[l];
   int64_t off = block_off[blockIdx.x];
-  int64_t end = bd_min(n, off + KD_CHUNK_ELEMS);
+  int64_t end = bd_min(n, off + BDBNN_CHUNK_ELEMS);
   const float* S = ws.ptr[l];
   const float* T = wt.ptr[l];
   double s = 0;
@@ -37,15 +33,15 @@ __global__ void weight_kd_fwd_kernel(TensorListArg ws_meta, PtrList2 ws,
   if (threadIdx.x == 0) atomicAdd(out, red[0] / (double)n);
 }
 
-__global__ void weight_kd_bwd_kernel(TensorListArg wt_meta, PtrList2 wt,
-                                     PtrList2 grads,
+__global__ void weight_kd_bwd_kernel(TensorListArg wt_meta, PtrList wt,
+                                     PtrList grads,
                                      const int* __restrict__ block_tensor,
                                      const int64_t* __restrict__ block_off,
                                      const float* __restrict__ gscale) {
   int l = block_tensor[blockIdx.x];
   int64_t n = wt_meta.numel[l];
   int64_t off = block_off[blockIdx.x];
-  int64_t end = bd_min(n, off + KD_CHUNK_ELEMS);
+  int64_t end = bd_min(n, off + BDBNN_CHUNK_ELEMS);
   const float* T = wt.ptr[l];
   float* G = grads.ptr[l];
   float coef = -gscale[0] / (float)n;
@@ -54,7 +50,7 @@ __global__ void weight_kd_bwd_kernel(TensorListArg wt_meta, PtrList2 wt,
 }
 
 extern "C" void bdbnn_weight_kd_fwd(const TensorListArg* meta,
-                                    const PtrList2* ws, const PtrList2* wt,
+                                    const PtrList* ws, const PtrList* wt,
                                     const int* bt, const int64_t* bo,
                                     int n_blocks, double* out,
                                     hipStream_t stream) {
@@ -64,7 +60,7 @@ extern "C" void bdbnn_weight_kd_fwd(const TensorListArg* meta,
 }
 
 extern "C" void bdbnn_weight_kd_bwd(const TensorListArg* meta,
-                                    const PtrList2* wt, const PtrList2* grads,
+                                    const PtrList* wt, const PtrList* grads,
                                     const int* bt, const int64_t* bo,
                                     int n_blocks, const float* gscale,
                                     hipStream_t stream) {

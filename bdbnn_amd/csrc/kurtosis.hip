@@ -12,12 +12,8 @@
 //                (z_i^3 - mean(z^3) - z_i*kurt*n/(n-1)).
 //
 // Work split: a host-built schedule maps each block to (tensor l, offset);
-// every block covers CHUNK_ELEMS contiguous elements of its tensor.
+// every block covers BDBNN_CHUNK_ELEMS contiguous elements of its tensor.
 #include "common.h"
-
-constexpr int64_t KURT_CHUNK_ELEMS = 32 * 1024;
-
-struct GradPtrs { float* ptr[BDBNN_MAX_TENSORS]; };
 
 __global__ void kurt_moments_kernel(TensorListArg lists,
                                     const int* __restrict__ block_tensor,
@@ -27,7 +23,7 @@ __global__ void kurt_moments_kernel(TensorListArg lists,
   const float* w = lists.ptr[l];
   int64_t n = lists.numel[l];
   int64_t off = block_off[blockIdx.x];
-  int64_t end = bd_min(n, off + KURT_CHUNK_ELEMS);
+  int64_t end = bd_min(n, off + BDBNN_CHUNK_ELEMS);
   double s1 = 0, s2 = 0, s3 = 0, s4 = 0;
   for (int64_t i = off + threadIdx.x; i < end; i += blockDim.x) {
     double v = (double)w[i];
@@ -77,7 +73,7 @@ __global__ void kurt_finalize_kernel(TensorListArg lists,
   kurts[l] = (float)kurt;
 }
 
-__global__ void kurt_bwd_kernel(TensorListArg lists, GradPtrs gp,
+__global__ void kurt_bwd_kernel(TensorListArg lists, PtrList gp,
                                 const int* __restrict__ block_tensor,
                                 const int64_t* __restrict__ block_off,
                                 const float* __restrict__ stats,
@@ -92,7 +88,7 @@ __global__ void kurt_bwd_kernel(TensorListArg lists, GradPtrs gp,
   float coef = gscale[0] * 2.f * (kurt - targets[l]) * 4.f / (float(n) * sigma);
   float knn = kurt * float(n) / float(n - 1);
   int64_t off = block_off[blockIdx.x];
-  int64_t end = bd_min(n, off + KURT_CHUNK_ELEMS);
+  int64_t end = bd_min(n, off + BDBNN_CHUNK_ELEMS);
   for (int64_t i = off + threadIdx.x; i < end; i += blockDim.x) {
     float z = (w[i] - mu) / sigma;
     g[i] = coef * (z * z * z - z3m - z * knn);
@@ -116,7 +112,7 @@ extern "C" void bdbnn_kurtosis_fwd(const TensorListArg* lists,
 }
 
 extern "C" void bdbnn_kurtosis_bwd(const TensorListArg* lists,
-                                   const GradPtrs* gp,
+                                   const PtrList* gp,
                                    const int* block_tensor_dev,
                                    const int64_t* block_off_dev,
                                    int n_blocks, const float* stats,

@@ -5,10 +5,6 @@
 // schedule is built on the host (cached per optimizer in Python).
 #include "common.h"
 
-struct PtrList { float* ptr[BDBNN_MAX_TENSORS]; };
-
-constexpr int64_t OPT_CHUNK_ELEMS = 32 * 1024;
-
 __global__ void fused_sgd_kernel(TensorListArg params_meta, PtrList p,
                                  PtrList g, PtrList buf,
                                  const int* __restrict__ block_tensor,
@@ -17,7 +13,7 @@ __global__ void fused_sgd_kernel(TensorListArg params_meta, PtrList p,
   int l = block_tensor[blockIdx.x];
   int64_t n = params_meta.numel[l];
   int64_t off = block_off[blockIdx.x];
-  int64_t end = bd_min(n, off + OPT_CHUNK_ELEMS);
+  int64_t end = bd_min(n, off + BDBNN_CHUNK_ELEMS);
   float* P = p.ptr[l];
   const float* G = g.ptr[l];
   float* B = buf.ptr[l];
@@ -38,7 +34,7 @@ __global__ void fused_adam_kernel(TensorListArg params_meta, PtrList p,
   int l = block_tensor[blockIdx.x];
   int64_t n = params_meta.numel[l];
   int64_t off = block_off[blockIdx.x];
-  int64_t end = bd_min(n, off + OPT_CHUNK_ELEMS);
+  int64_t end = bd_min(n, off + BDBNN_CHUNK_ELEMS);
   float* P = p.ptr[l];
   const float* G = g.ptr[l];
   float* M = m1.ptr[l];

@@ -21,7 +21,7 @@
 //
 // The input is consumed as an NHWC bf16 tensor padded to 4 channels
 // (x4, produced by stem_pack_x4 below: one cheap pass per step);
-// weights via stem_pack_w4 / grads back via stem_unpack_dw4.
+// weights via stem_pack_w4 / grads back via stem_fold_dw4.
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(512, 2) void stem_fwd_kernel(
   }
 }
 
-// ---------------- operand pack / unpack helpers ----------------
+// ---------------- operand pack helpers ----------------
 
 // x (N,3,H,W any layout via strides handled host-side: expects NHWC
 // contiguous bf16/f32) -> x4 (N,H,W,4) bf16 with channel 3 zeroed
@@ -230,26 +230,6 @@ extern "C" void bdbnn_stem_pack_w4(const float* w, void* w4T,
       w, (__bf16*)w4T);
 }
 
-// dw4T fp32 [64][224] -> dw (64,3,7,7 fp32)
-__global__ void stem_unpack_dw4_kernel(const float* __restrict__ dw4T,
-                                       float* __restrict__ dw) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;   // ((k*3+c)*7+dy)*7+dx
-  if (i >= ST_K * 3 * 49) return;
-  int dx = i % 7;
-  int rem = i / 7;
-  int dy = rem % 7;
-  rem /= 7;
-  int c = rem % 3;
-  int k = rem / 3;
-  dw[i] = dw4T[k * ST_KD + dy * 32 + dx * 4 + c];
-}
-
-extern "C" void bdbnn_stem_unpack_dw4(const float* dw4T, float* dw,
-                                      hipStream_t stream) {
-  stem_unpack_dw4_kernel<<<(ST_K * 3 * 49 + 255) / 256, 256, 0, stream>>>(
-      dw4T, dw);
-}
-
 extern "C" void bdbnn_stem_fwd(const void* x4, const void* w4T, void* out,
                                int N, int H, int W, hipStream_t stream) {
   StemParams p;
@@ -271,7 +251,7 @@ extern "C" void bdbnn_stem_fwd(const void* x4, const void* w4T, void* out,
 //   pT: the im2col expansion of the staged input rows (8-gather b128
 //       writes; invalid slots are written as zeros).
 // Each block walks a contiguous tile range and stores its fp32 partial
-// slab [64][224]; stem_unpack_dw4 folds the slabs (no atomics).
+// slab [64][224]; stem_fold_dw4 folds the slabs (no atomics).
 __global__ __launch_bounds__(512, 2) void stem_wrw_kernel(
     const __bf16* __restrict__ x4, const __bf16* __restrict__ g,
     float* __restrict__ dwslab, StemParams p, int n_blocks) {

@@ -769,6 +769,76 @@ def test_dtype_only_bindings_reject(dtype):
         nat.ste_mask_mul(odd, odd, 0, 0.0, 0.0)
 
 
+def test_multi_tensor_lists_must_pair_with_the_leading_list():
+    """fused_sgd / fused_adam / weight_kd_fwd index every list by the
+    leading list's tensor number and element count: a short list, a
+    non-fp32 entry or a short tensor raises before any launch, and a
+    correct call afterwards still matches torch.optim.SGD."""
+    from bdbnn_amd.ops.optim import FusedSGD
+    nat = _nat()
+    torch.manual_seed(80)
+    new = lambda n=1000: torch.randn(n, device="cuda")
+    p, g, buf = ([new() for _ in range(3)] for _ in range(3))
+    before = [t.clone() for t in p]
+    with pytest.raises(RuntimeError):                 # two grads for three
+        nat.fused_sgd(p, g[:2], buf, 0.1, 0.9, 1e-4)
+    with pytest.raises(RuntimeError):                 # one grad bf16
+        nat.fused_sgd(p, [g[0], g[1].bfloat16(), g[2]], buf, 0.1, 0.9, 1e-4)
+    with pytest.raises(RuntimeError):                 # one buffer short
+        nat.fused_sgd(p, g, [buf[0], new(999), buf[2]], 0.1, 0.9, 1e-4)
+    with pytest.raises(RuntimeError):                 # short m2 list
+        nat.fused_adam(p, g, buf, [new(), new()], 1e-3, 0.9, 0.999, 1e-8,
+                       0.0, 0.1, 0.001)
+    with pytest.raises(RuntimeError):                 # two teachers for three
+        nat.weight_kd_fwd(p, g[:2])
+    torch.cuda.synchronize()
+    for t, b in zip(p, before):
+        assert torch.equal(t, b), "a rejected call wrote its parameters"
+
+    ps = [t.clone().requires_grad_(True) for t in p]
+    ref = [t.detach().clone().requires_grad_(True) for t in ps]
+    for t, r, gi in zip(ps, ref, g):
+        t.grad = gi.clone()
+        r.grad = gi.clone()
+    opt = FusedSGD(ps, lr=0.1, momentum=0.9, weight_decay=1e-4)
+    topt = torch.optim.SGD(ref, lr=0.1, momentum=0.9, weight_decay=1e-4)
+    for _ in range(3):
+        opt.step()
+        topt.step()
+        for t in ps + ref:
+            t.grad = t.grad * 0.9 + 0.01  # evolve grads deterministically
+    for t, r in zip(ps, ref):
+        assert torch.allclose(t, r, atol=1e-5, rtol=1e-5)
+
+
+def test_bn_act_fwd_train_rejects_mistyped_statistics():
+    """The running stats are written through float pointers and the
+    pre-accumulated sums read through them: fp64 running_mean, one running
+    stat without the other, pre_s1 without pre_s2 raise; the valid call
+    on the same (2, 8, 4, 4) bf16 input stays within the oracle's bounds."""
+    nat = _nat()
+    case = _Case((2, 8, 4), BF16, "relu", False, seed=81)
+    x = case.x.cuda()
+    assert x.shape == (2, 8, 4, 4)
+    assert x.is_contiguous(memory_format=torch.channels_last)
+    gamma, beta = case.gamma.cuda(), case.beta.cuda()
+    rm, rv = case.rm0.cuda(), case.rv0.cuda()
+    call = lambda rm, rv, s1=None, s2=None: nat.bn_act_fwd_train(
+        x, None, gamma, beta, None, rm, rv, MOMENTUM, BN_EPS, ACTS["relu"],
+        s1, s2, False)
+    with pytest.raises(RuntimeError):
+        call(rm.double(), rv)
+    with pytest.raises(RuntimeError):
+        call(rm, None)
+    with pytest.raises(RuntimeError):
+        call(None, rv)
+    with pytest.raises(RuntimeError):
+        call(rm, rv, torch.zeros(32, 8, device="cuda"), None)
+    torch.cuda.synchronize()
+    assert torch.equal(rm.cpu(), case.rm0) and torch.equal(rv.cpu(), case.rv0)
+    _run_native(case, False, "cpu", "guards-2x8x4-bf16-relu")
+
+
 @pytest.mark.parametrize("which", [0, 2], ids=["C4", "fp16"])
 def test_unsupported_inputs_take_the_torch_composition(which):
     """fused_bn_act and ChannelPReLU on a 4-channel and on an fp16 CUDA
