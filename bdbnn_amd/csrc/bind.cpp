@@ -108,12 +108,24 @@ TensorListArg make_meta(const std::vector<at::Tensor>& ts) {
   return a;
 }
 
+// Two dense tensors whose element i in physical memory is the same logical
+// element: equal strides, or both dense in the same memory format (size-1
+// dimensions leave the strides themselves ambiguous).
+bool same_layout(const at::Tensor& a, const at::Tensor& b) {
+  if (a.strides() == b.strides()) return true;
+  if (a.is_contiguous() && b.is_contiguous()) return true;
+  return a.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+         b.is_contiguous(at::MemoryFormat::ChannelsLast);
+}
+
 // A further list of a fused call.  The kernels index it by the leading
-// list's tensor number and element count, so it must pair up with `lead`
-// (the make_meta of the leading list) one to one.
+// list's tensor number and element count and pair the elements over
+// physical memory, so it must pair up with `lead_ts` (the leading list,
+// whose make_meta is `lead`) one to one, in size and in layout.
 PtrList make_ptrs(const std::vector<at::Tensor>& ts,
-                  const TensorListArg& lead) {
-  TORCH_CHECK((int)ts.size() == lead.n,
+                  const TensorListArg& lead,
+                  const std::vector<at::Tensor>& lead_ts) {
+  TORCH_CHECK((int)ts.size() == lead.n && (int)lead_ts.size() == lead.n,
               "fused multi-tensor ops need lists of equal length");
   PtrList p;
   for (size_t i = 0; i < ts.size(); ++i) {
@@ -123,9 +135,22 @@ PtrList make_ptrs(const std::vector<at::Tensor>& ts,
                     ts[i].numel() == lead.numel[i],
                 "fused multi-tensor ops need dense fp32 CUDA tensors sized "
                 "like the leading list's");
+    TORCH_CHECK(same_layout(ts[i], lead_ts[i]),
+                "fused multi-tensor ops pair elements over physical memory: "
+                "tensor ", i, " has strides ", ts[i].strides(),
+                " against the leading list's ", lead_ts[i].strides());
     p.ptr[i] = ts[i].data_ptr<float>();
   }
   return p;
+}
+
+// the logit dtypes loss.hip has kernels for; anything else would be read
+// as fp32 (ops/losses.py routes other dtypes to the torch formulas)
+void check_logits(const at::Tensor& s, const char* who) {
+  TORCH_CHECK(s.is_cuda() && s.dim() == 2 &&
+                  (s.scalar_type() == at::kFloat ||
+                   s.scalar_type() == at::kBFloat16),
+              who, ": logits must be a (B,C) fp32 or bf16 CUDA tensor");
 }
 
 // fp32 contiguous copy of a per-channel tensor (a no-op for fp32 [C])
@@ -426,8 +451,10 @@ at::Tensor stem_conv_wrw(const at::Tensor& x4, const at::Tensor& gy) {
 
 std::vector<at::Tensor> kd_logit_fwd(const at::Tensor& s,
                                      const at::Tensor& t) {
-  TORCH_CHECK(s.is_cuda() && s.dim() == 2 && s.sizes() == t.sizes(),
-              "kd_logit: (B,C) logits");
+  check_logits(s, "kd_logit_fwd");
+  TORCH_CHECK(t.is_cuda() && s.sizes() == t.sizes(),
+              "kd_logit_fwd: teacher logits must be a CUDA tensor of the "
+              "student's shape");
   auto sc = s.contiguous();
   auto tc = t.to(s.scalar_type()).contiguous();
   int B = (int)s.size(0), C = (int)s.size(1);
@@ -442,6 +469,14 @@ std::vector<at::Tensor> kd_logit_fwd(const at::Tensor& s,
 
 at::Tensor kd_logit_bwd(const at::Tensor& s, const at::Tensor& t,
                         const at::Tensor& stats, double gscale) {
+  check_logits(s, "kd_logit_bwd");
+  // t and stats are what kd_logit_fwd returned: read as they are
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == s.scalar_type() &&
+                  t.sizes() == s.sizes() && t.is_contiguous(),
+              "kd_logit_bwd: t must be contiguous, of s's dtype and shape");
+  TORCH_CHECK(stats.is_cuda() && stats.scalar_type() == at::kFloat &&
+                  stats.is_contiguous() && stats.numel() == 4 * s.size(0),
+              "kd_logit_bwd: stats must be contiguous fp32 [B,4]");
   auto sc = s.contiguous();
   int B = (int)s.size(0), C = (int)s.size(1);
   auto ds = at::empty_like(sc);
@@ -452,8 +487,10 @@ at::Tensor kd_logit_bwd(const at::Tensor& s, const at::Tensor& t,
 }
 
 std::vector<at::Tensor> ce_fwd(const at::Tensor& s, const at::Tensor& y) {
-  TORCH_CHECK(s.is_cuda() && s.dim() == 2 && y.scalar_type() == at::kLong,
-              "ce: (B,C) logits + int64 targets");
+  check_logits(s, "ce_fwd");
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kLong && y.dim() == 1 &&
+                  y.size(0) == s.size(0),
+              "ce_fwd: targets must be an int64 CUDA tensor [B]");
   auto sc = s.contiguous();
   auto yc = y.contiguous();
   int B = (int)s.size(0), C = (int)s.size(1);
@@ -468,10 +505,18 @@ std::vector<at::Tensor> ce_fwd(const at::Tensor& s, const at::Tensor& y) {
 
 at::Tensor ce_bwd(const at::Tensor& s, const at::Tensor& y,
                   const at::Tensor& stats, double gscale) {
+  check_logits(s, "ce_bwd");
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kLong && y.dim() == 1 &&
+                  y.size(0) == s.size(0),
+              "ce_bwd: targets must be an int64 CUDA tensor [B]");
+  TORCH_CHECK(stats.is_cuda() && stats.scalar_type() == at::kFloat &&
+                  stats.is_contiguous() && stats.numel() == s.size(0),
+              "ce_bwd: stats must be contiguous fp32 [B]");
   auto sc = s.contiguous();
+  auto yc = y.contiguous();   // the kernel indexes y[b] with unit stride
   int B = (int)s.size(0), C = (int)s.size(1);
   auto ds = at::empty_like(sc);
-  bdbnn_ce_bwd(sc.data_ptr(), y.data_ptr<int64_t>(),
+  bdbnn_ce_bwd(sc.data_ptr(), yc.data_ptr<int64_t>(),
                stats.data_ptr<float>(), ds.data_ptr(),
                (float)(gscale / B), B, C, is_bf16(sc), cur_stream());
   return ds;
@@ -1221,7 +1266,7 @@ std::vector<at::Tensor> kurtosis_bwd(const std::vector<at::Tensor>& ws,
   for (auto& w : ws)  // preserve_format: grad layout == weight layout
     grads.push_back(at::empty_like(w, w.options(),
                                    at::MemoryFormat::Preserve));
-  auto gp = make_ptrs(grads, meta);
+  auto gp = make_ptrs(grads, meta, ws);
   auto tgt = targets.to(dev, at::kFloat).contiguous();
   auto st = stats.contiguous();
   // gscale is a 0-dim DEVICE tensor: no host sync in the backward
@@ -1239,10 +1284,10 @@ at::Tensor weight_kd_fwd(const std::vector<at::Tensor>& ws,
                          const std::vector<at::Tensor>& wt) {
   auto meta = make_meta(ws);
   auto sched = build_schedule(ws, BDBNN_CHUNK_ELEMS, ws[0].device());
-  auto s_ptr = make_ptrs(ws, meta);
-  std::vector<at::Tensor> wt_c;
-  for (auto& t : wt) wt_c.push_back(t.contiguous());
-  auto t_ptr = make_ptrs(wt_c, meta);
+  auto s_ptr = make_ptrs(ws, meta, ws);
+  // the teacher as given: ops/kd.py aligns its layout to the student's,
+  // and make_ptrs rejects a pair whose layouts differ
+  auto t_ptr = make_ptrs(wt, meta, ws);
   auto out = at::zeros({}, ws[0].options().dtype(at::kDouble));
   bdbnn_weight_kd_fwd(&meta, &s_ptr, &t_ptr, sched.bt.data_ptr<int>(),
                       sched.bo.data_ptr<int64_t>(), sched.n_blocks,
@@ -1254,12 +1299,12 @@ std::vector<at::Tensor> weight_kd_bwd(const std::vector<at::Tensor>& wt,
                                       const at::Tensor& gscale) {
   auto meta = make_meta(wt);
   auto sched = build_schedule(wt, BDBNN_CHUNK_ELEMS, wt[0].device());
-  auto t_ptr = make_ptrs(wt, meta);
+  auto t_ptr = make_ptrs(wt, meta, wt);
   std::vector<at::Tensor> grads;
   for (auto& t : wt)
     grads.push_back(at::empty_like(t, t.options(),
                                    at::MemoryFormat::Preserve));
-  auto gp = make_ptrs(grads, meta);
+  auto gp = make_ptrs(grads, meta, wt);
   auto gs = gscale.to(wt[0].device(), at::kFloat).contiguous();
   bdbnn_weight_kd_bwd(&meta, &t_ptr, &gp, sched.bt.data_ptr<int>(),
                       sched.bo.data_ptr<int64_t>(), sched.n_blocks,
@@ -1275,9 +1320,9 @@ void fused_sgd(const std::vector<at::Tensor>& p,
                double wd) {
   auto meta = make_meta(p);
   auto sched = build_schedule(p, BDBNN_CHUNK_ELEMS, p[0].device());
-  auto pp = make_ptrs(p, meta);
-  auto gg = make_ptrs(g, meta);   // python aligns grad layout to the param's
-  auto bb = make_ptrs(buf, meta);
+  auto pp = make_ptrs(p, meta, p);
+  auto gg = make_ptrs(g, meta, p);  // python aligns grad layout to the param's
+  auto bb = make_ptrs(buf, meta, p);
   bdbnn_fused_sgd(&meta, &pp, &gg, &bb, sched.bt.data_ptr<int>(),
                   sched.bo.data_ptr<int64_t>(), sched.n_blocks, (float)lr,
                   (float)momentum, (float)wd, cur_stream());
@@ -1290,10 +1335,10 @@ void fused_adam(const std::vector<at::Tensor>& p,
                 double beta2, double eps, double wd, double bc1, double bc2) {
   auto meta = make_meta(p);
   auto sched = build_schedule(p, BDBNN_CHUNK_ELEMS, p[0].device());
-  auto pp = make_ptrs(p, meta);
-  auto gg = make_ptrs(g, meta);   // python aligns grad layout to the param's
-  auto mm1 = make_ptrs(m1, meta);
-  auto mm2 = make_ptrs(m2, meta);
+  auto pp = make_ptrs(p, meta, p);
+  auto gg = make_ptrs(g, meta, p);  // python aligns grad layout to the param's
+  auto mm1 = make_ptrs(m1, meta, p);
+  auto mm2 = make_ptrs(m2, meta, p);
   bdbnn_fused_adam(&meta, &pp, &gg, &mm1, &mm2, sched.bt.data_ptr<int>(),
                    sched.bo.data_ptr<int64_t>(), sched.n_blocks, (float)lr,
                    (float)beta1, (float)beta2, (float)eps, (float)wd,

@@ -34,9 +34,8 @@ class DistributionLoss(_loss._Loss):
     def forward(self, stud_output, teacher_output):
         if teacher_output.requires_grad:
             raise ValueError("real network output should not require gradients.")
-        if (stud_output.is_cuda and stud_output.dim() == 2
-                and _C.has_native()):
-            from .losses import fused_logit_kd
+        from .losses import fused_logit_kd, native_logits
+        if native_logits(stud_output):
             return fused_logit_kd(stud_output, teacher_output)
         log_p_s = F.log_softmax(stud_output, dim=1)
         p_t = F.softmax(teacher_output, dim=1)

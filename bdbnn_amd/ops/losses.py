@@ -9,6 +9,24 @@ import torch.nn.functional as F
 from .. import _C
 
 
+def native_logits(logits):
+    """True when the loss.hip kernels take these logits: a (B, C) CUDA
+    tensor in fp32 or bf16, the two types they have a template for.  Any
+    other dtype (fp16, fp64) goes to the torch formula; the binding
+    raises on it, since it would be read as fp32."""
+    return (logits.is_cuda and logits.dim() == 2
+            and logits.dtype in (torch.float32, torch.bfloat16)
+            and _C.has_native())
+
+
+def _scale_grad(ds, g):
+    """ds * g for the 0-dim fp32 upstream gradient g, formed in fp32: torch
+    would round g itself to a bf16 ds's type before the product."""
+    if ds.dtype == torch.float32:
+        return ds * g
+    return (ds.float() * g).to(ds.dtype)
+
+
 class _LogitKDFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, s, t):
@@ -21,7 +39,7 @@ class _LogitKDFn(torch.autograd.Function):
     def backward(ctx, g):
         s, tc, stats = ctx.saved_tensors
         ds = _C.native_required().kd_logit_bwd(s, tc, stats, 1.0)
-        return ds * g, None
+        return _scale_grad(ds, g), None
 
 
 def fused_logit_kd(stud_logits, teacher_logits):
@@ -41,14 +59,14 @@ class _CEFn(torch.autograd.Function):
     def backward(ctx, g):
         s, y, stats = ctx.saved_tensors
         ds = _C.native_required().ce_bwd(s, y, stats, 1.0)
-        return ds * g, None
+        return _scale_grad(ds, g), None
 
 
 class FusedCrossEntropy(nn.Module):
     """nn.CrossEntropyLoss(mean) with a fused HIP kernel on the GPU."""
 
     def forward(self, logits, target):
-        if (logits.is_cuda and logits.dim() == 2
-                and target.dtype == torch.long and _C.has_native()):
+        if (native_logits(logits) and target.dtype == torch.long
+                and target.dim() == 1):
             return _CEFn.apply(logits, target)
         return F.cross_entropy(logits, target)

@@ -27,6 +27,17 @@ def _match_layout(t, like):
     return t.contiguous()
 
 
+def _state_like(state, key, p):
+    """state[key] in p's layout.  A loaded state dict keeps the strides it
+    was saved with, and the fused kernels pair state and parameter over
+    physical memory: re-lay it out once and keep the result."""
+    t = state[key]
+    if t.stride() != p.stride():
+        t = _match_layout(t, p)
+        state[key] = t
+    return t
+
+
 class FusedSGD(torch.optim.Optimizer):
     """SGD with momentum + weight decay; multi-tensor fused step on GPU."""
 
@@ -50,7 +61,7 @@ class FusedSGD(torch.optim.Optimizer):
                     state["momentum_buffer"] = torch.zeros_like(p)
                 ps.append(p)
                 gs.append(p.grad)
-                bufs.append(state["momentum_buffer"])
+                bufs.append(_state_like(state, "momentum_buffer", p))
             if not ps:
                 continue
             if ps[0].is_cuda and _C.has_native():
@@ -84,8 +95,10 @@ class FusedAdam(torch.optim.Optimizer):
             beta1, beta2 = group["betas"]
             eps = group["eps"]
             wd = group["weight_decay"]
-            ps, gs, m1s, m2s = [], [], [], []
-            step_t = None
+            # the bias correction depends on the parameter's own step count
+            # (one that had no grad on some step lags behind): one fused
+            # call per distinct count, a single call in the normal case
+            by_step = {}
             for p in group["params"]:
                 if p.grad is None:
                     continue
@@ -95,30 +108,30 @@ class FusedAdam(torch.optim.Optimizer):
                     state["exp_avg_sq"] = torch.zeros_like(p)
                     state["step"] = 0
                 state["step"] += 1
-                step_t = state["step"]
+                ps, gs, m1s, m2s = by_step.setdefault(
+                    int(state["step"]), ([], [], [], []))
                 ps.append(p)
                 gs.append(p.grad)
-                m1s.append(state["exp_avg"])
-                m2s.append(state["exp_avg_sq"])
-            if not ps:
-                continue
-            bc1 = 1 - beta1 ** step_t
-            bc2 = 1 - beta2 ** step_t
-            if ps[0].is_cuda and _C.has_native():
-                gs = [_match_layout(g.float(), p) for p, g in zip(ps, gs)]
-                nat = _C.native_required()
-                for i in range(0, len(ps), 64):  # kernel-arg tensor cap
-                    nat.fused_adam(ps[i:i + 64], gs[i:i + 64],
-                                   m1s[i:i + 64], m2s[i:i + 64],
-                                   lr, beta1, beta2, eps, wd, bc1, bc2)
-            else:
-                for p, g, m, v in zip(ps, gs, m1s, m2s):
-                    if wd != 0:
-                        g = g.add(p, alpha=wd)
-                    m.mul_(beta1).add_(g, alpha=1 - beta1)
-                    v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
-                    denom = (v / bc2).sqrt_().add_(eps)
-                    p.addcdiv_(m / bc1, denom, value=-lr)
+                m1s.append(_state_like(state, "exp_avg", p))
+                m2s.append(_state_like(state, "exp_avg_sq", p))
+            for step_t, (ps, gs, m1s, m2s) in by_step.items():
+                bc1 = 1 - beta1 ** step_t
+                bc2 = 1 - beta2 ** step_t
+                if ps[0].is_cuda and _C.has_native():
+                    gs = [_match_layout(g.float(), p) for p, g in zip(ps, gs)]
+                    nat = _C.native_required()
+                    for i in range(0, len(ps), 64):  # kernel-arg tensor cap
+                        nat.fused_adam(ps[i:i + 64], gs[i:i + 64],
+                                       m1s[i:i + 64], m2s[i:i + 64],
+                                       lr, beta1, beta2, eps, wd, bc1, bc2)
+                else:
+                    for p, g, m, v in zip(ps, gs, m1s, m2s):
+                        if wd != 0:
+                            g = g.add(p, alpha=wd)
+                        m.mul_(beta1).add_(g, alpha=1 - beta1)
+                        v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+                        denom = (v / bc2).sqrt_().add_(eps)
+                        p.addcdiv_(m / bc1, denom, value=-lr)
         return loss
 
 
