@@ -175,14 +175,6 @@ int bdbnn_conv_wgrad2_s2(const void* g, const uint64_t* planes, float* dwT,
                          int ks, int N, int H, int W, int C, int K,
                          hipStream_t stream);
 
-// ---- conv_dgrad.hip, conv_wgrad.hip (experimental v1) ----
-void bdbnn_conv_dgrad(const void* g, const uint32_t* wp, const float* alpha,
-                      void* dx, int N, int H, int W, int C, int K, int CW,
-                      hipStream_t stream);
-void bdbnn_conv_wgrad(const void* g, const uint32_t* xp, float* dw, int N,
-                      int H, int W, int C, int K, int CW,
-                      hipStream_t stream);
-
 // ---- kurtosis.hip ----
 void bdbnn_kurtosis_fwd(const TensorListArg* lists,
                         const int* block_tensor_dev,

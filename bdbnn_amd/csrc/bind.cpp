@@ -1190,49 +1190,6 @@ at::Tensor conv_wgrad2_s2(const at::Tensor& g, const at::Tensor& planes,
   return dwT;
 }
 
-// ---------------- experimental MFMA dgrad (v1, kept for A/B) -------------
-
-at::Tensor conv_dgrad(const at::Tensor& g, const at::Tensor& wp,
-                      const at::Tensor& alpha, int64_t C) {
-  TORCH_CHECK(g.is_cuda() && g.dim() == 4 &&
-                  g.scalar_type() == at::kBFloat16 &&
-                  g.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_dgrad: bf16 channels_last grad");
-  int N = (int)g.size(0), K = (int)g.size(1);
-  int H = (int)g.size(2), W = (int)g.size(3);
-  TORCH_CHECK(wp.size(0) == K && wp.size(1) == 3 && wp.size(2) == 3,
-              "conv_dgrad: packed 3x3 weights");
-  TORCH_CHECK(((int64_t)N * H * W) % 128 == 0 && C % 64 == 0 && K % 16 == 0,
-              "conv_dgrad: shape constraints");
-  int CW = (int)wp.size(3);
-  auto dx = at::empty({N, C, H, W}, g.options(),
-                      at::MemoryFormat::ChannelsLast);
-  bdbnn_conv_dgrad(g.data_ptr(), (const uint32_t*)wp.data_ptr<int>(),
-                   alpha.data_ptr<float>(), dx.data_ptr(), N, H, W, (int)C,
-                   K, CW, cur_stream());
-  return dx;
-}
-
-at::Tensor conv_wgrad(const at::Tensor& g, const at::Tensor& xp,
-                      int64_t C) {
-  TORCH_CHECK(g.is_cuda() && g.dim() == 4 &&
-                  g.scalar_type() == at::kBFloat16 &&
-                  g.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_wgrad: bf16 channels_last grad");
-  int N = (int)g.size(0), K = (int)g.size(1);
-  int H = (int)g.size(2), W = (int)g.size(3);
-  TORCH_CHECK(xp.size(0) == N && xp.size(1) == H && xp.size(2) == W,
-              "conv_wgrad: packed activations shape");
-  TORCH_CHECK(((int64_t)N * H * W) % 16 == 0 && K % 32 == 0 && C % 32 == 0,
-              "conv_wgrad: shape constraints");
-  int CW = (int)xp.size(3);
-  auto dw = at::zeros({K, C, 3, 3}, g.options().dtype(at::kFloat));
-  bdbnn_conv_wgrad(g.data_ptr(), (const uint32_t*)xp.data_ptr<int>(),
-                   dw.data_ptr<float>(), N, H, W, (int)C, K, CW,
-                   cur_stream());
-  return dw;
-}
-
 // ---------------- kurtosis ----------------
 
 std::vector<at::Tensor> kurtosis_fwd(const std::vector<at::Tensor>& ws,
@@ -1440,10 +1397,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("W"), py::arg("ks"));
   m.def("wgrad_finish_s2", &wgrad_finish_s2,
         "dwT slab sum + transpose to [K][C][ks][ks] + |w|<=1 STE mask");
-  m.def("conv_dgrad", &conv_dgrad,
-        "EXPERIMENTAL MFMA bf16 dgrad (3x3/s1/p1, packed weights)");
-  m.def("conv_wgrad", &conv_wgrad,
-        "EXPERIMENTAL MFMA bf16 wgrad (3x3/s1/p1, packed activations)");
   m.def("kurtosis_fwd", &kurtosis_fwd, "fused multi-tensor kurtosis fwd");
   m.def("kurtosis_bwd", &kurtosis_bwd, "fused multi-tensor kurtosis bwd");
   m.def("weight_kd_fwd", &weight_kd_fwd, "fused weight-space KD fwd");

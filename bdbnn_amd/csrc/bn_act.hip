@@ -18,6 +18,7 @@
 #include "common.h"
 #include "vec8.h"
 #include "bn_affine.h"
+#include "act_masks.h"
 
 // ---- pass 1: per-channel sum / sumsq ----
 template <typename T>
@@ -26,10 +27,8 @@ __global__ void bn_stats_kernel(const T* __restrict__ x,
                                 float* __restrict__ s2,
                                 int64_t n_pix, int C) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* l1 = (float*)smem_raw;
-  float* l2 = l1 + C;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) { l1[c] = 0.f; l2[c] = 0.f; }
-  __syncthreads();
+  float* lds = (float*)smem_raw;   // [2][C]
+  chan_sums_zero<2>(lds, C);
   ChanMap m = chan_map8(C);
   float a1[8] = {}, a2[8] = {};
   // 4 independent pixel loads in flight per wave: one blocking load per
@@ -54,19 +53,9 @@ __global__ void bn_stats_kernel(const T* __restrict__ x,
 #pragma unroll
     for (int j = 0; j < 8; ++j) { a1[j] += v0[j]; a2[j] += v0[j] * v0[j]; }
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    atomicAdd(&l1[m.c0 + j], a1[j]);
-    atomicAdd(&l2[m.c0 + j], a2[j]);
-  }
-  __syncthreads();
-  // 32-way sliced output ([32][C], folded by bn_finalize): full-grid
-  // atomics onto C words serialize ~2048-deep otherwise
-  const int off = (blockIdx.x & 31) * C;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    if (l1[c] != 0.f) atomicAdd(&s1[off + c], l1[c]);
-    if (l2[c] != 0.f) atomicAdd(&s2[off + c], l2[c]);
-  }
+  chan_sums_add<2>(lds, C, m.c0, {a1, a2});
+  // 32-way sliced output (s1, s2: [32][C] each, folded by bn_finalize)
+  chan_sums_flush<2, true>(lds, C, {s1, s2}, 1, C);
 }
 
 // ---- finalize: mean/invstd + running-stat update ----
@@ -103,9 +92,8 @@ __global__ void bn_finalize_kernel(const float* __restrict__ s1,
 // assembled in the epilogue from the ROUNDED stored values (bit-exact
 // with csrc/pack.hip sign_mask_pack_kernel on the written tensor), so
 // that conv never re-reads the activation to pack it.  Each thread owns
-// 8 consecutive channels -> one byte of each plane; the 4 lanes of a
-// 32-channel word are consecutive (C % 32 == 0 => threads-per-row % 4
-// == 0) and combine with intra-wave shuffles, lane (tid&3)==0 stores.
+// 8 consecutive channels -> one byte of each plane, combined across the 4
+// lanes of a word by pack_sign_mask8 (act_masks.h).
 template <typename T, int ACT, bool PACK>
 __global__ void bn_act_fwd_kernel(const T* __restrict__ x,
                                   const T* __restrict__ skip,
@@ -145,25 +133,10 @@ __global__ void bn_act_fwd_kernel(const T* __restrict__ x,
     store8(out, i, o);
     if (zout != nullptr) store8(zout, i, z);
     if constexpr (PACK) {
-      unsigned both = 0;   // sign byte | mask byte << 8
+      float r[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float r = (sizeof(T) == 2) ? bf16_to_f32(f32_to_bf16(o[j])) : o[j];
-        both |= (r >= 0.f ? 1u : 0u) << j;
-        both |= (fabsf(r) <= 1.f ? 1u : 0u) << (8 + j);
-      }
-      unsigned b1 = __shfl_down(both, 1);
-      unsigned b2 = __shfl_down(both, 2);
-      unsigned b3 = __shfl_down(both, 3);
-      if (sub == 0) {
-        uint32_t sw = (both & 0xffu) | ((b1 & 0xffu) << 8) |
-                      ((b2 & 0xffu) << 16) | ((b3 & 0xffu) << 24);
-        uint32_t mw = ((both >> 8) & 0xffu) | (((b1 >> 8) & 0xffu) << 8) |
-                      (((b2 >> 8) & 0xffu) << 16) |
-                      (((b3 >> 8) & 0xffu) << 24);
-        xpk[p * CW + cw] = sw;
-        mpk[p * CW + cw] = mw;
-      }
+      for (int j = 0; j < 8; ++j) r[j] = round_storage<T>(o[j]);
+      pack_sign_mask8(r, sub, xpk, mpk, p * CW + cw);
     }
   }
 }
@@ -180,13 +153,8 @@ __global__ void bn_act_bwd_reduce_kernel(
     const float* __restrict__ invstd, const float* __restrict__ a,
     float* __restrict__ sums, int64_t n_pix, int C) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* r0 = (float*)smem_raw;
-  float* r1 = r0 + C;
-  float* r2 = r1 + C;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    r0[c] = 0.f; r1[c] = 0.f; r2[c] = 0.f;
-  }
-  __syncthreads();
+  float* lds = (float*)smem_raw;   // [3][C]
+  chan_sums_zero<3>(lds, C);
   ChanMap m = chan_map8(C);
   float mu[8], is[8], av[8];
 #pragma unroll
@@ -239,19 +207,10 @@ __global__ void bn_act_bwd_reduce_kernel(
     BN_RED_BODY(dyv, zv, xv)
   }
 #undef BN_RED_BODY
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    atomicAdd(&r0[m.c0 + j], s0[j]);
-    atomicAdd(&r1[m.c0 + j], s1[j]);
-    if (ACT == 1) atomicAdd(&r2[m.c0 + j], s2[j]);
-  }
-  __syncthreads();
-  float* my = sums + (blockIdx.x & 31) * (C * 3);
-  for (int cc = threadIdx.x; cc < C; cc += blockDim.x) {
-    if (r0[cc] != 0.f) atomicAdd(&my[cc * 3 + 0], r0[cc]);
-    if (r1[cc] != 0.f) atomicAdd(&my[cc * 3 + 1], r1[cc]);
-    if (r2[cc] != 0.f) atomicAdd(&my[cc * 3 + 2], r2[cc]);
-  }
+  // da (row 2) is PReLU's only; the row stays zero and is skipped otherwise
+  if (ACT == 1) chan_sums_add<3>(lds, C, m.c0, {s0, s1, s2});
+  else          chan_sums_add<2>(lds, C, m.c0, {s0, s1});
+  chan_sums_flush<3, true>(lds, C, {sums, sums + 1, sums + 2}, 3, C * 3);
 }
 
 // fold the 32 slices -> [C][3] (tiny; launched right after the reduce)
@@ -366,86 +325,6 @@ __global__ void bn_act_eval_kernel(const T* __restrict__ x,
 
 // ---------------- launchers ----------------
 
-template <typename T>
-static void launch_fwd(const void* x, const void* skip, const float* mean,
-                       const float* invstd, const float* gamma,
-                       const float* beta, const float* a, void* out,
-                       void* zout, int64_t n_pix, int C, int act_kind,
-                       uint32_t* xpk, uint32_t* mpk, int grid,
-                       hipStream_t stream) {
-  auto X = (const T*)x; auto S = (const T*)skip;
-  auto O = (T*)out; auto Z = (T*)zout;
-#define BN_FWD(ACT)                                                       \
-  {                                                                       \
-    if (xpk != nullptr)                                                   \
-      bn_act_fwd_kernel<T, ACT, true><<<grid, 256, 0, stream>>>(          \
-          X, S, mean, invstd, gamma, beta, a, O, Z, n_pix, C, xpk, mpk);  \
-    else                                                                  \
-      bn_act_fwd_kernel<T, ACT, false><<<grid, 256, 0, stream>>>(         \
-          X, S, mean, invstd, gamma, beta, a, O, Z, n_pix, C, xpk, mpk);  \
-  }
-  if (act_kind == 1) BN_FWD(1)
-  else if (act_kind == 2) BN_FWD(2)
-  else BN_FWD(0)
-#undef BN_FWD
-}
-
-template <typename T>
-static void launch_bwd_reduce(const void* dy, const void* z, const void* x,
-                              const float* mean, const float* invstd,
-                              const float* a, float* sums, int64_t n_pix,
-                              int C, int act_kind, int grid, size_t lds,
-                              hipStream_t stream) {
-  auto DY = (const T*)dy; auto ZZ = (const T*)z; auto X = (const T*)x;
-  if (act_kind == 1)
-    bn_act_bwd_reduce_kernel<T, 1><<<grid, 256, lds, stream>>>(
-        DY, ZZ, X, mean, invstd, a, sums, n_pix, C);
-  else if (act_kind == 2)
-    bn_act_bwd_reduce_kernel<T, 2><<<grid, 256, lds, stream>>>(
-        DY, ZZ, X, mean, invstd, a, sums, n_pix, C);
-  else
-    bn_act_bwd_reduce_kernel<T, 0><<<grid, 256, lds, stream>>>(
-        DY, ZZ, X, mean, invstd, a, sums, n_pix, C);
-}
-
-template <typename T>
-static void launch_bwd_apply(const void* dy, const void* z, const void* x,
-                             const float* mean, const float* invstd,
-                             const float* gamma, const float* a,
-                             const float* sums, void* dx, void* dskip,
-                             int64_t n_pix, int C, int act_kind, float inv_n,
-                             int grid, hipStream_t stream) {
-  auto DY = (const T*)dy; auto ZZ = (const T*)z; auto X = (const T*)x;
-  auto DX = (T*)dx; auto DS = (T*)dskip;
-  if (act_kind == 1)
-    bn_act_bwd_apply_kernel<T, 1><<<grid, 256, 0, stream>>>(
-        DY, ZZ, X, mean, invstd, gamma, a, sums, DX, DS, n_pix, C, inv_n);
-  else if (act_kind == 2)
-    bn_act_bwd_apply_kernel<T, 2><<<grid, 256, 0, stream>>>(
-        DY, ZZ, X, mean, invstd, gamma, a, sums, DX, DS, n_pix, C, inv_n);
-  else
-    bn_act_bwd_apply_kernel<T, 0><<<grid, 256, 0, stream>>>(
-        DY, ZZ, X, mean, invstd, gamma, a, sums, DX, DS, n_pix, C, inv_n);
-}
-
-template <typename T>
-static void launch_eval(const void* x, const void* skip, const float* rm,
-                        const float* rv, const float* gamma,
-                        const float* beta, const float* a, void* out,
-                        int64_t n_pix, int C, int act_kind, float eps,
-                        int grid, hipStream_t stream) {
-  auto X = (const T*)x; auto S = (const T*)skip; auto O = (T*)out;
-  if (act_kind == 1)
-    bn_act_eval_kernel<T, 1><<<grid, 256, 0, stream>>>(
-        X, S, rm, rv, gamma, beta, a, O, n_pix, C, eps);
-  else if (act_kind == 2)
-    bn_act_eval_kernel<T, 2><<<grid, 256, 0, stream>>>(
-        X, S, rm, rv, gamma, beta, a, O, n_pix, C, eps);
-  else
-    bn_act_eval_kernel<T, 0><<<grid, 256, 0, stream>>>(
-        X, S, rm, rv, gamma, beta, a, O, n_pix, C, eps);
-}
-
 extern "C" void bdbnn_bn_stats(const void* x, float* s1, float* s2,
                                int64_t n, int C, bool bf16,
                                hipStream_t stream) {
@@ -454,12 +333,11 @@ extern "C" void bdbnn_bn_stats(const void* x, float* s1, float* s2,
   int64_t n_pix = n / C;
   int grid = grid_pix8(n_pix, C);
   size_t lds = 2 * sizeof(float) * C;
-  if (bf16)
-    bn_stats_kernel<uint16_t><<<grid, 256, lds, stream>>>(
-        (const uint16_t*)x, s1, s2, n_pix, C);
-  else
-    bn_stats_kernel<float><<<grid, 256, lds, stream>>>(
-        (const float*)x, s1, s2, n_pix, C);
+  with_dtype(bf16, [&](auto t) {
+    using T = decltype(t);
+    bn_stats_kernel<T><<<grid, 256, lds, stream>>>((const T*)x, s1, s2,
+                                                   n_pix, C);
+  });
 }
 
 extern "C" void bdbnn_bn_finalize(const float* s1, const float* s2,
@@ -481,12 +359,17 @@ extern "C" void bdbnn_bn_act_fwd(const void* x, const void* skip,
                                  hipStream_t stream) {
   int64_t n_pix = n / C;
   int grid = grid_pix8(n_pix, C);
-  if (bf16)
-    launch_fwd<uint16_t>(x, skip, mean, invstd, gamma, beta, a, out, zout,
-                         n_pix, C, act_kind, xpk, mpk, grid, stream);
-  else
-    launch_fwd<float>(x, skip, mean, invstd, gamma, beta, a, out, zout,
-                      n_pix, C, act_kind, xpk, mpk, grid, stream);
+  with_dtype(bf16, [&](auto t) {
+    with_int<1, 2, 0>(act_kind, [&](auto act) {
+      with_bool(xpk != nullptr, [&](auto pack) {
+        using T = decltype(t);
+        bn_act_fwd_kernel<T, decltype(act)::value, decltype(pack)::value>
+            <<<grid, 256, 0, stream>>>((const T*)x, (const T*)skip, mean,
+                                       invstd, gamma, beta, a, (T*)out,
+                                       (T*)zout, n_pix, C, xpk, mpk);
+      });
+    });
+  });
 }
 
 extern "C" void bdbnn_bn_act_bwd_reduce(const void* dy, const void* z,
@@ -499,12 +382,15 @@ extern "C" void bdbnn_bn_act_bwd_reduce(const void* dy, const void* z,
   int64_t n_pix = n / C;
   int grid = grid_pix8(n_pix, C);
   size_t lds = 3 * sizeof(float) * C;
-  if (bf16)
-    launch_bwd_reduce<uint16_t>(dy, z, x, mean, invstd, a, sums32, n_pix, C,
-                                act_kind, grid, lds, stream);
-  else
-    launch_bwd_reduce<float>(dy, z, x, mean, invstd, a, sums32, n_pix, C,
-                             act_kind, grid, lds, stream);
+  with_dtype(bf16, [&](auto t) {
+    with_int<1, 2, 0>(act_kind, [&](auto act) {
+      using T = decltype(t);
+      bn_act_bwd_reduce_kernel<T, decltype(act)::value>
+          <<<grid, 256, lds, stream>>>((const T*)dy, (const T*)z,
+                                       (const T*)x, mean, invstd, a, sums32,
+                                       n_pix, C);
+    });
+  });
   bn_fold_sums_kernel<<<(C * 3 + 255) / 256, 256, 0, stream>>>(sums32, sums,
                                                                C * 3);
 }
@@ -525,13 +411,15 @@ extern "C" void bdbnn_bn_act_bwd_apply(const void* dy, const void* z,
                                        hipStream_t stream) {
   int64_t n_pix = n / C;
   int grid = grid_pix8(n_pix, C);
-  if (bf16)
-    launch_bwd_apply<uint16_t>(dy, z, x, mean, invstd, gamma, a, sums, dx,
-                               dskip, n_pix, C, act_kind, inv_n, grid,
-                               stream);
-  else
-    launch_bwd_apply<float>(dy, z, x, mean, invstd, gamma, a, sums, dx,
-                            dskip, n_pix, C, act_kind, inv_n, grid, stream);
+  with_dtype(bf16, [&](auto t) {
+    with_int<1, 2, 0>(act_kind, [&](auto act) {
+      using T = decltype(t);
+      bn_act_bwd_apply_kernel<T, decltype(act)::value>
+          <<<grid, 256, 0, stream>>>((const T*)dy, (const T*)z, (const T*)x,
+                                     mean, invstd, gamma, a, sums, (T*)dx,
+                                     (T*)dskip, n_pix, C, inv_n);
+    });
+  });
 }
 
 extern "C" void bdbnn_bn_act_eval(const void* x, const void* skip,
@@ -542,10 +430,12 @@ extern "C" void bdbnn_bn_act_eval(const void* x, const void* skip,
                                   hipStream_t stream) {
   int64_t n_pix = n / C;
   int grid = grid_pix8(n_pix, C);
-  if (bf16)
-    launch_eval<uint16_t>(x, skip, rm, rv, gamma, beta, a, out, n_pix, C,
-                          act_kind, eps, grid, stream);
-  else
-    launch_eval<float>(x, skip, rm, rv, gamma, beta, a, out, n_pix, C,
-                       act_kind, eps, grid, stream);
+  with_dtype(bf16, [&](auto t) {
+    with_int<1, 2, 0>(act_kind, [&](auto act) {
+      using T = decltype(t);
+      bn_act_eval_kernel<T, decltype(act)::value><<<grid, 256, 0, stream>>>(
+          (const T*)x, (const T*)skip, rm, rv, gamma, beta, a, (T*)out,
+          n_pix, C, eps);
+    });
+  });
 }

@@ -27,10 +27,8 @@
 #include "common.h"
 #include "vec8.h"
 #include "bn_affine.h"
-
-struct BnPoolParams {
-  int N, C, H, W, Ho, Wo, ks, stride, pad;
-};
+#include "act_masks.h"
+#include "pool_common.h"
 
 // chan_map8 on the XCD-remapped block id
 __device__ __forceinline__ ChanMap pool_map8(int C) {
@@ -61,14 +59,14 @@ __device__ __forceinline__ void load_scale_shift(
 // independent loads in flight per thread.  KS == 0: any window, one
 // blocking load per tap.
 // PACK: sign + clip-mask bitplanes of the pooled (already rounded)
-// values, with the shuffle scheme of bn_act_fwd_kernel<PACK>.
+// values, by pack_sign_mask8 as in bn_act_fwd_kernel<PACK>.
 template <typename T, int KS, bool PACK>
 __global__ void __launch_bounds__(256) bn_relu_maxpool_fwd_kernel(
     const T* __restrict__ x, const float* __restrict__ mean,
     const float* __restrict__ invstd, const float* __restrict__ gamma,
     const float* __restrict__ beta, T* __restrict__ out,
     unsigned char* __restrict__ idx, uint32_t* __restrict__ xpk,
-    uint32_t* __restrict__ mpk, BnPoolParams p, int n_opix) {
+    uint32_t* __restrict__ mpk, PoolParams p, int n_opix) {
   ChanMap m = pool_map8(p.C);
   float sc[8], sh[8];
   load_scale_shift(mean, invstd, gamma, beta, m.c0, sc, sh);
@@ -126,26 +124,7 @@ __global__ void __launch_bounds__(256) bn_relu_maxpool_fwd_kernel(
     iw.y = (unsigned)bi[4] | ((unsigned)bi[5] << 8) |
            ((unsigned)bi[6] << 16) | ((unsigned)bi[7] << 24);
     *(uint2*)(idx + op * p.C + m.c0) = iw;
-    if constexpr (PACK) {
-      unsigned both = 0;   // sign byte | mask byte << 8
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        both |= (best[j] >= 0.f ? 1u : 0u) << j;
-        both |= (fabsf(best[j]) <= 1.f ? 1u : 0u) << (8 + j);
-      }
-      unsigned b1 = __shfl_down(both, 1);
-      unsigned b2 = __shfl_down(both, 2);
-      unsigned b3 = __shfl_down(both, 3);
-      if (sub == 0) {
-        uint32_t sw = (both & 0xffu) | ((b1 & 0xffu) << 8) |
-                      ((b2 & 0xffu) << 16) | ((b3 & 0xffu) << 24);
-        uint32_t mw = ((both >> 8) & 0xffu) | (((b1 >> 8) & 0xffu) << 8) |
-                      (((b2 >> 8) & 0xffu) << 16) |
-                      (((b3 >> 8) & 0xffu) << 24);
-        xpk[op * CW + cw] = sw;
-        mpk[op * CW + cw] = mw;
-      }
-    }
+    if constexpr (PACK) pack_sign_mask8(best, sub, xpk, mpk, op * CW + cw);
   }
 }
 
@@ -165,14 +144,13 @@ __device__ __forceinline__ int idx_byte(const uint2& q, int j) {
 template <typename T, bool W2>
 __device__ __forceinline__ void pool_gather_dy(
     const T* __restrict__ dy, const unsigned char* __restrict__ idx,
-    const BnPoolParams& p, int n, int iy, int ix, int c0, float acc[8]) {
+    const PoolParams& p, int n, int iy, int ix, int c0, float acc[8]) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = 0.f;
   // windows (oy, ox) with iy0 <= iy < iy0+ks
-  int oy_lo = max(0, (iy + p.pad - p.ks + p.stride) / p.stride);
-  int oy_hi = min(p.Ho - 1, (iy + p.pad) / p.stride);
-  int ox_lo = max(0, (ix + p.pad - p.ks + p.stride) / p.stride);
-  int ox_hi = min(p.Wo - 1, (ix + p.pad) / p.stride);
+  int oy_lo, oy_hi, ox_lo, ox_hi;
+  pool_window_range(p, iy, p.Ho, oy_lo, oy_hi);
+  pool_window_range(p, ix, p.Wo, ox_lo, ox_hi);
   const int64_t img = (int64_t)n * p.Ho;
   if constexpr (W2) {
     float g[4][8];
@@ -231,7 +209,7 @@ __device__ __forceinline__ void pool_gather_dy(
 template <typename T, int GATHER, typename F>
 __device__ __forceinline__ void pool_bwd_sweep(
     const T* __restrict__ dy, const unsigned char* __restrict__ idx,
-    const T* __restrict__ x, const BnPoolParams& p, const ChanMap& m,
+    const T* __restrict__ x, const PoolParams& p, const ChanMap& m,
     const float sc[8], const float sh[8], F body) {
   if constexpr (GATHER == 2) {
     const int Wq = p.Wo, HqWq = p.Ho * p.Wo;   // Ho = ceil(H/2) quad rows
@@ -322,14 +300,10 @@ __global__ void __launch_bounds__(256) bn_relu_maxpool_bwd_reduce_kernel(
     const T* __restrict__ x, const float* __restrict__ mean,
     const float* __restrict__ invstd, const float* __restrict__ gamma,
     const float* __restrict__ beta, float* __restrict__ sums,
-    BnPoolParams p) {
+    PoolParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* r0 = (float*)smem_raw;
-  float* r1 = r0 + p.C;
-  for (int c = threadIdx.x; c < p.C; c += blockDim.x) {
-    r0[c] = 0.f; r1[c] = 0.f;
-  }
-  __syncthreads();
+  float* lds = (float*)smem_raw;   // [2][C]
+  chan_sums_zero<2>(lds, p.C);
   ChanMap m = pool_map8(p.C);
   float sc[8], sh[8], mu[8], is[8];
   load_scale_shift(mean, invstd, gamma, beta, m.c0, sc, sh);
@@ -348,17 +322,8 @@ __global__ void __launch_bounds__(256) bn_relu_maxpool_bwd_reduce_kernel(
           s1[j] += dz[j] * xhat;
         }
       });
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    atomicAdd(&r0[m.c0 + j], s0[j]);
-    atomicAdd(&r1[m.c0 + j], s1[j]);
-  }
-  __syncthreads();
-  float* my = sums + (blockIdx.x & 31) * (p.C * 2);
-  for (int cc = threadIdx.x; cc < p.C; cc += blockDim.x) {
-    if (r0[cc] != 0.f) atomicAdd(&my[cc * 2 + 0], r0[cc]);
-    if (r1[cc] != 0.f) atomicAdd(&my[cc * 2 + 1], r1[cc]);
-  }
+  chan_sums_add<2>(lds, p.C, m.c0, {s0, s1});
+  chan_sums_flush<2, true>(lds, p.C, {sums, sums + 1}, 2, p.C * 2);
 }
 
 // ---- backward pass 2: dx ----
@@ -369,7 +334,7 @@ __global__ void __launch_bounds__(256) bn_relu_maxpool_bwd_apply_kernel(
     const T* __restrict__ x, const float* __restrict__ mean,
     const float* __restrict__ invstd, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ sums,
-    T* __restrict__ dx, BnPoolParams p, float inv_n) {
+    T* __restrict__ dx, PoolParams p, float inv_n) {
   ChanMap m = pool_map8(p.C);
   float sc[8], sh[8], mu[8], is[8], sdz_n[8], sdzx_n[8];
   load_scale_shift(mean, invstd, gamma, beta, m.c0, sc, sh);
@@ -403,42 +368,26 @@ static int pool_gather_mode(int ks, int stride, int pad) {
 
 // ---------------- launchers ----------------
 
-template <typename T>
-static void launch_pool_fwd(const void* x, const float* mean,
-                            const float* invstd, const float* gamma,
-                            const float* beta, void* out, unsigned char* idx,
-                            uint32_t* xpk, uint32_t* mpk, BnPoolParams p,
-                            int n_opix, int grid, hipStream_t stream) {
-  auto X = (const T*)x; auto O = (T*)out;
-#define POOL_FWD(KS)                                                      \
-  {                                                                       \
-    if (xpk != nullptr)                                                   \
-      bn_relu_maxpool_fwd_kernel<T, KS, true><<<grid, 256, 0, stream>>>(  \
-          X, mean, invstd, gamma, beta, O, idx, xpk, mpk, p, n_opix);     \
-    else                                                                  \
-      bn_relu_maxpool_fwd_kernel<T, KS, false><<<grid, 256, 0, stream>>>( \
-          X, mean, invstd, gamma, beta, O, idx, xpk, mpk, p, n_opix);     \
-  }
-  if (p.ks == 3) POOL_FWD(3)
-  else if (p.ks == 2) POOL_FWD(2)
-  else POOL_FWD(0)
-#undef POOL_FWD
-}
-
 extern "C" void bdbnn_bn_relu_maxpool_fwd(
     const void* x, const float* mean, const float* invstd,
     const float* gamma, const float* beta, void* out, unsigned char* idx,
     uint32_t* xpk, uint32_t* mpk, int N, int C, int H, int W, int Ho, int Wo,
     int ks, int stride, int pad, bool bf16, hipStream_t stream) {
-  BnPoolParams p{N, C, H, W, Ho, Wo, ks, stride, pad};
+  PoolParams p{N, C, H, W, Ho, Wo, ks, stride, pad};
   int n_opix = N * Ho * Wo;
   int grid = grid_pix8(n_opix, C);
-  if (bf16)
-    launch_pool_fwd<uint16_t>(x, mean, invstd, gamma, beta, out, idx, xpk,
-                              mpk, p, n_opix, grid, stream);
-  else
-    launch_pool_fwd<float>(x, mean, invstd, gamma, beta, out, idx, xpk, mpk,
-                           p, n_opix, grid, stream);
+  with_dtype(bf16, [&](auto t) {
+    with_int<3, 2, 0>(ks, [&](auto k) {
+      with_bool(xpk != nullptr, [&](auto pack) {
+        using T = decltype(t);
+        bn_relu_maxpool_fwd_kernel<T, decltype(k)::value,
+                                   decltype(pack)::value>
+            <<<grid, 256, 0, stream>>>((const T*)x, mean, invstd, gamma,
+                                       beta, (T*)out, idx, xpk, mpk, p,
+                                       n_opix);
+      });
+    });
+  });
 }
 
 // sums32: [32][C][2] scratch, sums: [C][2] result
@@ -449,23 +398,18 @@ extern "C" void bdbnn_bn_relu_maxpool_bwd_reduce(
     int W, int Ho, int Wo, int ks, int stride, int pad, bool bf16,
     hipStream_t stream) {
   (void)hipMemsetAsync(sums32, 0, sizeof(float) * 32 * C * 2, stream);
-  BnPoolParams p{N, C, H, W, Ho, Wo, ks, stride, pad};
+  PoolParams p{N, C, H, W, Ho, Wo, ks, stride, pad};
   int mode = pool_gather_mode(ks, stride, pad);
   int grid = grid_pix8(mode == 2 ? N * Ho * Wo : N * H * W, C);
   size_t lds = 2 * sizeof(float) * C;
-#define POOL_RED(T, G)                                                    \
-  bn_relu_maxpool_bwd_reduce_kernel<T, G><<<grid, 256, lds, stream>>>(    \
-      (const T*)dy, idx, (const T*)x, mean, invstd, gamma, beta, sums32, p)
-  if (bf16) {
-    if (mode == 2) POOL_RED(uint16_t, 2);
-    else if (mode == 1) POOL_RED(uint16_t, 1);
-    else POOL_RED(uint16_t, 0);
-  } else {
-    if (mode == 2) POOL_RED(float, 2);
-    else if (mode == 1) POOL_RED(float, 1);
-    else POOL_RED(float, 0);
-  }
-#undef POOL_RED
+  with_dtype(bf16, [&](auto t) {
+    with_int<2, 1, 0>(mode, [&](auto g) {
+      using T = decltype(t);
+      bn_relu_maxpool_bwd_reduce_kernel<T, decltype(g)::value>
+          <<<grid, 256, lds, stream>>>((const T*)dy, idx, (const T*)x, mean,
+                                       invstd, gamma, beta, sums32, p);
+    });
+  });
   bdbnn_bn_fold_sums(sums32, sums, C * 2, stream);
 }
 
@@ -475,22 +419,17 @@ extern "C" void bdbnn_bn_relu_maxpool_bwd_apply(
     const float* beta, const float* sums, void* dx, int N, int C, int H,
     int W, int Ho, int Wo, int ks, int stride, int pad, bool bf16,
     hipStream_t stream) {
-  BnPoolParams p{N, C, H, W, Ho, Wo, ks, stride, pad};
+  PoolParams p{N, C, H, W, Ho, Wo, ks, stride, pad};
   int mode = pool_gather_mode(ks, stride, pad);
   int grid = grid_pix8(mode == 2 ? N * Ho * Wo : N * H * W, C);
   float inv_n = (float)(1.0 / ((double)N * H * W));
-#define POOL_APPLY(T, G)                                                  \
-  bn_relu_maxpool_bwd_apply_kernel<T, G><<<grid, 256, 0, stream>>>(       \
-      (const T*)dy, idx, (const T*)x, mean, invstd, gamma, beta, sums,    \
-      (T*)dx, p, inv_n)
-  if (bf16) {
-    if (mode == 2) POOL_APPLY(uint16_t, 2);
-    else if (mode == 1) POOL_APPLY(uint16_t, 1);
-    else POOL_APPLY(uint16_t, 0);
-  } else {
-    if (mode == 2) POOL_APPLY(float, 2);
-    else if (mode == 1) POOL_APPLY(float, 1);
-    else POOL_APPLY(float, 0);
-  }
-#undef POOL_APPLY
+  with_dtype(bf16, [&](auto t) {
+    with_int<2, 1, 0>(mode, [&](auto g) {
+      using T = decltype(t);
+      bn_relu_maxpool_bwd_apply_kernel<T, decltype(g)::value>
+          <<<grid, 256, 0, stream>>>((const T*)dy, idx, (const T*)x, mean,
+                                     invstd, gamma, beta, sums, (T*)dx, p,
+                                     inv_n);
+    });
+  });
 }

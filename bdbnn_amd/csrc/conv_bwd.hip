@@ -14,7 +14,10 @@
 // same kernel with a value mask of the saved bf16 activation instead of
 // the bitplane (MODE template parameter, conv_dgrad2_x).
 //
-// Why v2 is fast where v1 (csrc/conv_dgrad.hip) was 4-6x behind MIOpen:
+// v1 was the round-1 seed: a correctness-first rocWMMA dgrad / wgrad pair
+// with a single-buffered ladder, never wired into an op.  It is gone; its
+// measurements stay in docs/R2_MFMA_CONV_BACKWARD.md.
+// Why v2 is fast where v1 was 4-6x behind MIOpen:
 //   * HALO staging: the block's g tile is staged ONCE per 64-channel
 //     chunk as a 2D zero-padded halo band, and all 9 taps read shifted
 //     windows of it from LDS — v1 re-staged the same g rows 9x.

@@ -2,6 +2,7 @@
 // conv_bwd_s2.hip: stride 2).
 #pragma once
 #include "common.h"
+#include "act_masks.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -69,14 +70,13 @@ __device__ __forceinline__ void wgrad2_combine_store(
 //   2  EDE  k*t*(1 - tanh^2(t*x))
 // Modes 1/2 depend on the VALUE of x, so they read the saved bf16 NHWC
 // activation `xin` at the very address they store dx to (`mp` unused);
-// semantics are those of ste_mask_mul_kernel (csrc/pack.hip).
+// mode 1 is ste_mask_mul_kernel's (csrc/pack.hip) react_poly_mask.
 template <int MODE>
 __device__ __forceinline__ float dgrad2_value_mask(float x, float et,
                                                    float ekt) {
   static_assert(MODE == 1 || MODE == 2, "value mask: mode 1 or 2");
   if constexpr (MODE == 1) {
-    return (x >= -1.f && x < 0.f) ? 2.f + 2.f * x
-         : (x >= 0.f && x < 1.f) ? 2.f - 2.f * x : 0.f;
+    return react_poly_mask(x);
   }
   // 1 - tanh^2(u) = 4e/(1+e)^2 with e = exp(-2|u|) in (0,1]: nothing
   // can overflow, and large |t*x| underflows cleanly to 0 (the

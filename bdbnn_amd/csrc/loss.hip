@@ -10,6 +10,7 @@
 //   KD: ds = g/B * (softmax(s) - softmax(t))
 //   CE: ds = g/B * (softmax(s) - onehot(y))
 #include "common.h"
+#include "vec8.h"
 
 __device__ __forceinline__ float block_reduce(float v, float* red, int op) {
   // op 0 = max, 1 = sum
@@ -27,12 +28,6 @@ __device__ __forceinline__ float block_reduce(float v, float* red, int op) {
   return r;
 }
 
-template <typename T>
-__device__ __forceinline__ float ld(const T* p, int64_t i) {
-  if constexpr (sizeof(T) == 2) return bf16_to_f32(((const uint16_t*)p)[i]);
-  else                          return ((const float*)p)[i];
-}
-
 // stats[b] = (m_s, lseZ_s, m_t, lseZ_t); out += loss_row / B
 template <typename T>
 __global__ void kd_logit_fwd_kernel(const T* __restrict__ s,
@@ -45,23 +40,23 @@ __global__ void kd_logit_fwd_kernel(const T* __restrict__ s,
   const T* tr = t + (int64_t)b * C;
   float ms = -3.4e38f, mt = -3.4e38f;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    ms = fmaxf(ms, ld(sr, c));
-    mt = fmaxf(mt, ld(tr, c));
+    ms = fmaxf(ms, ld1(sr, c));
+    mt = fmaxf(mt, ld1(tr, c));
   }
   ms = block_reduce(ms, red, 0);
   mt = block_reduce(mt, red, 0);
   float zs = 0.f, zt = 0.f;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    zs += expf(ld(sr, c) - ms);
-    zt += expf(ld(tr, c) - mt);
+    zs += expf(ld1(sr, c) - ms);
+    zt += expf(ld1(tr, c) - mt);
   }
   zs = block_reduce(zs, red, 1);
   zt = block_reduce(zt, red, 1);
   float lzs = logf(zs), lzt = logf(zt);
   float dot = 0.f;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    float pt = expf(ld(tr, c) - mt - lzt);
-    dot += pt * (ld(sr, c) - ms - lzs);
+    float pt = expf(ld1(tr, c) - mt - lzt);
+    dot += pt * (ld1(sr, c) - ms - lzs);
   }
   dot = block_reduce(dot, red, 1);
   if (threadIdx.x == 0) {
@@ -80,11 +75,10 @@ __global__ void kd_logit_bwd_kernel(const T* __restrict__ s,
   GRID_STRIDE(i, n) {
     int b = int(i / C);
     float lse_s = stats[b * 4 + 0], lse_t = stats[b * 4 + 1];
-    float ps = expf(ld(s, i) - lse_s);
-    float pt = expf(ld(t, i) - lse_t);
+    float ps = expf(ld1(s, i) - lse_s);
+    float pt = expf(ld1(t, i) - lse_t);
     float v = gscale * (ps - pt);
-    if constexpr (sizeof(T) == 2) ((uint16_t*)ds)[i] = f32_to_bf16(v);
-    else                          ((float*)ds)[i] = v;
+    st1(ds, i, v);
   }
 }
 
@@ -98,16 +92,16 @@ __global__ void ce_fwd_kernel(const T* __restrict__ s,
   const T* sr = s + (int64_t)b * C;
   float ms = -3.4e38f;
   for (int c = threadIdx.x; c < C; c += blockDim.x)
-    ms = fmaxf(ms, ld(sr, c));
+    ms = fmaxf(ms, ld1(sr, c));
   ms = block_reduce(ms, red, 0);
   float zs = 0.f;
   for (int c = threadIdx.x; c < C; c += blockDim.x)
-    zs += expf(ld(sr, c) - ms);
+    zs += expf(ld1(sr, c) - ms);
   zs = block_reduce(zs, red, 1);
   if (threadIdx.x == 0) {
     float lse = ms + logf(zs);
     stats[b] = lse;
-    atomicAdd(out, (lse - ld(sr, (int)y[b])) / (float)B);
+    atomicAdd(out, (lse - ld1(sr, (int)y[b])) / (float)B);
   }
 }
 
@@ -120,10 +114,9 @@ __global__ void ce_bwd_kernel(const T* __restrict__ s,
   GRID_STRIDE(i, n) {
     int b = int(i / C);
     int c = int(i % C);
-    float p = expf(ld(s, i) - stats[b]);
+    float p = expf(ld1(s, i) - stats[b]);
     float v = gscale * (p - (c == (int)y[b] ? 1.f : 0.f));
-    if constexpr (sizeof(T) == 2) ((uint16_t*)ds)[i] = f32_to_bf16(v);
-    else                          ((float*)ds)[i] = v;
+    st1(ds, i, v);
   }
 }
 
@@ -131,12 +124,11 @@ extern "C" void bdbnn_kd_logit_fwd(const void* s, const void* t,
                                    float* stats, float* out, int B, int C,
                                    bool bf16, hipStream_t stream) {
   hipMemsetAsync(out, 0, sizeof(float), stream);
-  if (bf16)
-    kd_logit_fwd_kernel<uint16_t><<<B, 256, 0, stream>>>(
-        (const uint16_t*)s, (const uint16_t*)t, stats, out, B, C);
-  else
-    kd_logit_fwd_kernel<float><<<B, 256, 0, stream>>>(
-        (const float*)s, (const float*)t, stats, out, B, C);
+  with_dtype(bf16, [&](auto tag) {
+    using T = decltype(tag);
+    kd_logit_fwd_kernel<T><<<B, 256, 0, stream>>>((const T*)s, (const T*)t,
+                                                  stats, out, B, C);
+  });
 }
 
 extern "C" void bdbnn_kd_logit_bwd(const void* s, const void* t,
@@ -145,25 +137,22 @@ extern "C" void bdbnn_kd_logit_bwd(const void* s, const void* t,
                                    hipStream_t stream) {
   int64_t n = (int64_t)B * C;
   int grid = (int)bd_min<int64_t>((n + 255) / 256, 2048);
-  if (bf16)
-    kd_logit_bwd_kernel<uint16_t><<<grid, 256, 0, stream>>>(
-        (const uint16_t*)s, (const uint16_t*)t, stats, (uint16_t*)ds,
-        gscale, n, C);
-  else
-    kd_logit_bwd_kernel<float><<<grid, 256, 0, stream>>>(
-        (const float*)s, (const float*)t, stats, (float*)ds, gscale, n, C);
+  with_dtype(bf16, [&](auto tag) {
+    using T = decltype(tag);
+    kd_logit_bwd_kernel<T><<<grid, 256, 0, stream>>>(
+        (const T*)s, (const T*)t, stats, (T*)ds, gscale, n, C);
+  });
 }
 
 extern "C" void bdbnn_ce_fwd(const void* s, const int64_t* y, float* stats,
                              float* out, int B, int C, bool bf16,
                              hipStream_t stream) {
   hipMemsetAsync(out, 0, sizeof(float), stream);
-  if (bf16)
-    ce_fwd_kernel<uint16_t><<<B, 256, 0, stream>>>(
-        (const uint16_t*)s, y, stats, out, B, C);
-  else
-    ce_fwd_kernel<float><<<B, 256, 0, stream>>>(
-        (const float*)s, y, stats, out, B, C);
+  with_dtype(bf16, [&](auto tag) {
+    using T = decltype(tag);
+    ce_fwd_kernel<T><<<B, 256, 0, stream>>>((const T*)s, y, stats, out, B,
+                                            C);
+  });
 }
 
 extern "C" void bdbnn_ce_bwd(const void* s, const int64_t* y,
@@ -171,10 +160,9 @@ extern "C" void bdbnn_ce_bwd(const void* s, const int64_t* y,
                              int B, int C, bool bf16, hipStream_t stream) {
   int64_t n = (int64_t)B * C;
   int grid = (int)bd_min<int64_t>((n + 255) / 256, 2048);
-  if (bf16)
-    ce_bwd_kernel<uint16_t><<<grid, 256, 0, stream>>>(
-        (const uint16_t*)s, y, stats, (uint16_t*)ds, gscale, n, C);
-  else
-    ce_bwd_kernel<float><<<grid, 256, 0, stream>>>(
-        (const float*)s, y, stats, (float*)ds, gscale, n, C);
+  with_dtype(bf16, [&](auto tag) {
+    using T = decltype(tag);
+    ce_bwd_kernel<T><<<grid, 256, 0, stream>>>((const T*)s, y, stats,
+                                               (T*)ds, gscale, n, C);
+  });
 }

@@ -10,6 +10,19 @@
 // to the popcount sum, a compile-known constant the epilogue subtracts.
 #include "common.h"
 #include "vec8.h"
+#include "act_masks.h"
+
+// body(c) for every channel bit c of a word that holds nbits channels: a
+// full word fully unrolled, a tail word (C % 32 != 0) as a plain loop.
+template <typename F>
+__device__ __forceinline__ void for_each_word_bit(int nbits, F body) {
+  if (nbits == 32) {
+#pragma unroll
+    for (int c = 0; c < 32; ++c) body(c);
+  } else {
+    for (int c = 0; c < nbits; ++c) body(c);
+  }
+}
 
 // ---------------- activation sign+pack ----------------
 // x: NHWC-contiguous (channels_last torch tensor), P = N*H*W pixels,
@@ -24,22 +37,9 @@ __global__ void sign_pack_kernel(const T* __restrict__ x,
     const T* px = x + p * C + cw * 32;
     int nbits = min(32, C - cw * 32);
     uint32_t bits = 0;
-    if (nbits == 32) {
-#pragma unroll
-      for (int c = 0; c < 32; ++c) {
-        float v;
-        if constexpr (sizeof(T) == 2) v = bf16_to_f32(((const uint16_t*)px)[c]);
-        else                          v = ((const float*)px)[c];
-        bits |= (v >= 0.f ? 1u : 0u) << c;
-      }
-    } else {
-      for (int c = 0; c < nbits; ++c) {
-        float v;
-        if constexpr (sizeof(T) == 2) v = bf16_to_f32(((const uint16_t*)px)[c]);
-        else                          v = ((const float*)px)[c];
-        bits |= (v >= 0.f ? 1u : 0u) << c;
-      }
-    }
+    for_each_word_bit(nbits, [&](int c) {
+      bits |= uint32_t(sign_bit(ld1(px, c))) << c;
+    });
     out[i] = bits;
   }
 }
@@ -50,12 +50,11 @@ extern "C" void bdbnn_sign_pack(const void* x, uint32_t* out, int64_t pixels,
   int64_t n_words = pixels * CW;
   int block = 256;
   int grid = (int)bd_min<int64_t>((n_words + block - 1) / block, 65535 * 8);
-  if (bf16)
-    sign_pack_kernel<uint16_t><<<grid, block, 0, stream>>>(
-        (const uint16_t*)x, out, n_words, C, CW);
-  else
-    sign_pack_kernel<float><<<grid, block, 0, stream>>>(
-        (const float*)x, out, n_words, C, CW);
+  with_dtype(bf16, [&](auto t) {
+    using T = decltype(t);
+    sign_pack_kernel<T><<<grid, block, 0, stream>>>((const T*)x, out,
+                                                    n_words, C, CW);
+  });
 }
 
 // ---------------- +-1 decode (for the dense MFMA backward) ----------------
@@ -69,7 +68,7 @@ __global__ void binsign_decode_kernel(const TI* __restrict__ x,
     float v[8], s[8];
     load8(x, i, v);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) s[j] = v[j] >= 0.f ? 1.f : -1.f;
+    for (int j = 0; j < 8; ++j) s[j] = sign_bit(v[j]) ? 1.f : -1.f;
     store8(y, i, s);
   }
 }
@@ -81,15 +80,12 @@ extern "C" void bdbnn_binsign_decode(const void* x, void* y, int64_t n,
   int64_t n8 = n / 8;   // callers guarantee n % 8 == 0
   int grid = (int)bd_min<int64_t>((n8 + block - 1) / block, 2048);
   n = n8;
-#define CASE(IB, OB, TI, TO)                                              \
-  if (in_bf16 == IB && out_bf16 == OB)                                    \
-    binsign_decode_kernel<TI, TO><<<grid, block, 0, stream>>>(            \
+  with_dtype2(in_bf16, out_bf16, [&](auto ti, auto to) {
+    using TI = decltype(ti);
+    using TO = decltype(to);
+    binsign_decode_kernel<TI, TO><<<grid, block, 0, stream>>>(
         (const TI*)x, (TO*)y, n);
-  CASE(false, false, float, float)
-  CASE(false, true, float, uint16_t)
-  CASE(true, false, uint16_t, float)
-  CASE(true, true, uint16_t, uint16_t)
-#undef CASE
+  });
 }
 
 // ---------------- STE/EDE mask multiply (quantizer backward) ----------------
@@ -109,10 +105,9 @@ __global__ void ste_mask_mul_kernel(const TG* __restrict__ g,
     for (int j = 0; j < 8; ++j) {
       float m;
       if (mode == 0) {
-        m = fabsf(xv[j]) <= 1.f ? 1.f : 0.f;
+        m = clip_bit(xv[j]) ? 1.f : 0.f;
       } else if (mode == 1) {
-        m = (xv[j] >= -1.f && xv[j] < 0.f) ? 2.f + 2.f * xv[j]
-          : (xv[j] >= 0.f && xv[j] < 1.f) ? 2.f - 2.f * xv[j] : 0.f;
+        m = react_poly_mask(xv[j]);
       } else {
         float th = tanhf(t * xv[j]);
         m = k * t * (1.f - th * th);
@@ -131,15 +126,12 @@ extern "C" void bdbnn_ste_mask_mul(const void* g, const void* x, void* y,
   int64_t n8 = n / 8;   // callers guarantee n % 8 == 0
   int grid = (int)bd_min<int64_t>((n8 + block - 1) / block, 2048);
   n = n8;
-#define CASE(GB, XB, TG, TX)                                              \
-  if (g_bf16 == GB && x_bf16 == XB)                                       \
-    ste_mask_mul_kernel<TG, TX><<<grid, block, 0, stream>>>(              \
+  with_dtype2(g_bf16, x_bf16, [&](auto tg, auto tx) {
+    using TG = decltype(tg);
+    using TX = decltype(tx);
+    ste_mask_mul_kernel<TG, TX><<<grid, block, 0, stream>>>(
         (const TG*)g, (const TX*)x, (TX*)y, n, mode, t, k);
-  CASE(false, false, float, float)
-  CASE(false, true, float, uint16_t)
-  CASE(true, false, uint16_t, float)
-  CASE(true, true, uint16_t, uint16_t)
-#undef CASE
+  });
 }
 
 // ---------------- weight pack ----------------
@@ -232,24 +224,11 @@ __global__ void sign_mask_pack_kernel(const T* __restrict__ x,
     const T* px = x + p * C + cw * 32;
     int nbits = min(32, C - cw * 32);
     uint32_t sbits = 0, mbits = 0;
-    if (nbits == 32) {
-#pragma unroll
-      for (int c = 0; c < 32; ++c) {
-        float v;
-        if constexpr (sizeof(T) == 2) v = bf16_to_f32(((const uint16_t*)px)[c]);
-        else                          v = ((const float*)px)[c];
-        sbits |= (v >= 0.f ? 1u : 0u) << c;
-        mbits |= (fabsf(v) <= 1.f ? 1u : 0u) << c;
-      }
-    } else {
-      for (int c = 0; c < nbits; ++c) {
-        float v;
-        if constexpr (sizeof(T) == 2) v = bf16_to_f32(((const uint16_t*)px)[c]);
-        else                          v = ((const float*)px)[c];
-        sbits |= (v >= 0.f ? 1u : 0u) << c;
-        mbits |= (fabsf(v) <= 1.f ? 1u : 0u) << c;
-      }
-    }
+    for_each_word_bit(nbits, [&](int c) {
+      float v = ld1(px, c);
+      sbits |= uint32_t(sign_bit(v)) << c;
+      mbits |= uint32_t(clip_bit(v)) << c;
+    });
     sp[i] = sbits;
     mp[i] = mbits;
   }
@@ -261,12 +240,11 @@ extern "C" void bdbnn_sign_mask_pack(const void* x, uint32_t* sp,
   int64_t n_words = pixels * CW;
   int block = 256;
   int grid = (int)bd_min<int64_t>((n_words + block - 1) / block, 4096);
-  if (bf16)
-    sign_mask_pack_kernel<uint16_t><<<grid, block, 0, stream>>>(
-        (const uint16_t*)x, sp, mp, n_words, C, CW);
-  else
-    sign_mask_pack_kernel<float><<<grid, block, 0, stream>>>(
-        (const float*)x, sp, mp, n_words, C, CW);
+  with_dtype(bf16, [&](auto t) {
+    using T = decltype(t);
+    sign_mask_pack_kernel<T><<<grid, block, 0, stream>>>(
+        (const T*)x, sp, mp, n_words, C, CW);
+  });
 }
 
 // ---------------- decode packed signs -> +-1 NHWC tensor ----------------
@@ -281,20 +259,9 @@ __global__ void decode_packed_kernel(const uint32_t* __restrict__ sp,
     int nbits = min(32, C - cw * 32);
     uint32_t bits = sp[i];
     TO* py = y + p * C + cw * 32;
-    if (nbits == 32) {
-#pragma unroll
-      for (int c = 0; c < 32; ++c) {
-        float s = (bits >> c) & 1 ? 1.f : -1.f;
-        if constexpr (sizeof(TO) == 2) ((uint16_t*)py)[c] = f32_to_bf16(s);
-        else                           ((float*)py)[c] = s;
-      }
-    } else {
-      for (int c = 0; c < nbits; ++c) {
-        float s = (bits >> c) & 1 ? 1.f : -1.f;
-        if constexpr (sizeof(TO) == 2) ((uint16_t*)py)[c] = f32_to_bf16(s);
-        else                           ((float*)py)[c] = s;
-      }
-    }
+    for_each_word_bit(nbits, [&](int c) {
+      st1(py, c, (bits >> c) & 1 ? 1.f : -1.f);
+    });
   }
 }
 
@@ -304,12 +271,11 @@ extern "C" void bdbnn_decode_packed(const uint32_t* sp, void* y,
   int64_t n_words = pixels * CW;
   int block = 256;
   int grid = (int)bd_min<int64_t>((n_words + block - 1) / block, 4096);
-  if (out_bf16)
-    decode_packed_kernel<uint16_t><<<grid, block, 0, stream>>>(
-        sp, (uint16_t*)y, n_words, C, CW);
-  else
-    decode_packed_kernel<float><<<grid, block, 0, stream>>>(
-        sp, (float*)y, n_words, C, CW);
+  with_dtype(out_bf16, [&](auto t) {
+    using TO = decltype(t);
+    decode_packed_kernel<TO><<<grid, block, 0, stream>>>(sp, (TO*)y, n_words,
+                                                         C, CW);
+  });
 }
 
 // ---------------- masked grad: dx = mask_bit ? g : 0 ----------------
@@ -325,26 +291,10 @@ __global__ void mask_mul_packed_kernel(const TG* __restrict__ g,
     uint32_t bits = mp[i];
     const TG* pg = g + p * C + cw * 32;
     TO* pd = dx + p * C + cw * 32;
-    if (nbits == 32) {
-#pragma unroll
-      for (int c = 0; c < 32; ++c) {
-        float gv;
-        if constexpr (sizeof(TG) == 2) gv = bf16_to_f32(((const uint16_t*)pg)[c]);
-        else                           gv = ((const float*)pg)[c];
-        float o = (bits >> c) & 1 ? gv : 0.f;
-        if constexpr (sizeof(TO) == 2) ((uint16_t*)pd)[c] = f32_to_bf16(o);
-        else                           ((float*)pd)[c] = o;
-      }
-    } else {
-      for (int c = 0; c < nbits; ++c) {
-        float gv;
-        if constexpr (sizeof(TG) == 2) gv = bf16_to_f32(((const uint16_t*)pg)[c]);
-        else                           gv = ((const float*)pg)[c];
-        float o = (bits >> c) & 1 ? gv : 0.f;
-        if constexpr (sizeof(TO) == 2) ((uint16_t*)pd)[c] = f32_to_bf16(o);
-        else                           ((float*)pd)[c] = o;
-      }
-    }
+    for_each_word_bit(nbits, [&](int c) {
+      float gv = ld1(pg, c);   // unconditional load, then select
+      st1(pd, c, (bits >> c) & 1 ? gv : 0.f);
+    });
   }
 }
 
@@ -355,15 +305,12 @@ extern "C" void bdbnn_mask_mul_packed(const void* g, const uint32_t* mp,
   int64_t n_words = pixels * CW;
   int block = 256;
   int grid = (int)bd_min<int64_t>((n_words + block - 1) / block, 4096);
-#define MCASE(GB, OB, TG, TO)                                             \
-  if (g_bf16 == GB && out_bf16 == OB)                                     \
-    mask_mul_packed_kernel<TG, TO><<<grid, block, 0, stream>>>(           \
+  with_dtype2(g_bf16, out_bf16, [&](auto tg, auto to) {
+    using TG = decltype(tg);
+    using TO = decltype(to);
+    mask_mul_packed_kernel<TG, TO><<<grid, block, 0, stream>>>(
         (const TG*)g, mp, (TO*)dx, n_words, C, CW);
-  MCASE(false, false, float, float)
-  MCASE(false, true, float, uint16_t)
-  MCASE(true, false, uint16_t, float)
-  MCASE(true, true, uint16_t, uint16_t)
-#undef MCASE
+  });
 }
 
 // ---------------- decode packed weights -> alpha * (+-1), NCHW ----------
@@ -384,9 +331,7 @@ __global__ void weight_decode_kernel(const uint32_t* __restrict__ wp,
     // w layout [K][C][KH][KW]: stride of c is T
     TO* pw = w + ((int64_t)k * C + cw * 32) * T + t;
     for (int c = 0; c < nbits; ++c) {
-      float v = (bits >> c) & 1 ? -al : al;  // inverted convention
-      if constexpr (sizeof(TO) == 2) ((uint16_t*)pw)[(int64_t)c * T] = f32_to_bf16(v);
-      else                           ((float*)pw)[(int64_t)c * T] = v;
+      st1(pw, (int64_t)c * T, (bits >> c) & 1 ? -al : al);  // inverted
     }
   }
 }
@@ -397,10 +342,9 @@ extern "C" void bdbnn_weight_decode(const uint32_t* wp, const float* alpha,
   int64_t n_words = (int64_t)K * T * CW;
   int block = 256;
   int grid = (int)bd_min<int64_t>((n_words + block - 1) / block, 4096);
-  if (out_bf16)
-    weight_decode_kernel<uint16_t><<<grid, block, 0, stream>>>(
-        wp, alpha, (uint16_t*)w, K, C, T, CW);
-  else
-    weight_decode_kernel<float><<<grid, block, 0, stream>>>(
-        wp, alpha, (float*)w, K, C, T, CW);
+  with_dtype(out_bf16, [&](auto t) {
+    using TO = decltype(t);
+    weight_decode_kernel<TO><<<grid, block, 0, stream>>>(wp, alpha, (TO*)w,
+                                                         K, C, T, CW);
+  });
 }

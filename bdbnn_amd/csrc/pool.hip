@@ -4,10 +4,7 @@
 // (profiles/r01_b512_steady_state.md).
 #include "common.h"
 #include "vec8.h"
-
-struct PoolParams {
-  int N, C, H, W, Ho, Wo, ks, stride, pad;
-};
+#include "pool_common.h"
 
 // thread owns 8 consecutive channels of one output pixel
 template <typename T>
@@ -56,10 +53,9 @@ __global__ void maxpool_bwd_kernel(const T* __restrict__ dy,
     int iy = rem / p.W, ix = rem % p.W;
     float acc[8] = {};
     // windows (oy, ox) with iy0 <= iy < iy0+ks
-    int oy_lo = max(0, (iy + p.pad - p.ks + p.stride) / p.stride);
-    int oy_hi = min(p.Ho - 1, (iy + p.pad) / p.stride);
-    int ox_lo = max(0, (ix + p.pad - p.ks + p.stride) / p.stride);
-    int ox_hi = min(p.Wo - 1, (ix + p.pad) / p.stride);
+    int oy_lo, oy_hi, ox_lo, ox_hi;
+    pool_window_range(p, iy, p.Ho, oy_lo, oy_hi);
+    pool_window_range(p, ix, p.Wo, ox_lo, ox_hi);
     for (int oy = oy_lo; oy <= oy_hi; ++oy)
       for (int ox = ox_lo; ox <= ox_hi; ++ox) {
         int t = (iy - (oy * p.stride - p.pad)) * p.ks +
@@ -82,12 +78,11 @@ extern "C" void bdbnn_maxpool_fwd(const void* x, void* out,
   PoolParams p{N, C, H, W, Ho, Wo, ks, stride, pad};
   int64_t n_opix = (int64_t)N * Ho * Wo;
   int grid = grid_pix8(n_opix, C);
-  if (bf16)
-    maxpool_fwd_kernel<uint16_t><<<grid, 256, 0, stream>>>(
-        (const uint16_t*)x, (uint16_t*)out, idx, p, n_opix);
-  else
-    maxpool_fwd_kernel<float><<<grid, 256, 0, stream>>>(
-        (const float*)x, (float*)out, idx, p, n_opix);
+  with_dtype(bf16, [&](auto t) {
+    using T = decltype(t);
+    maxpool_fwd_kernel<T><<<grid, 256, 0, stream>>>((const T*)x, (T*)out,
+                                                    idx, p, n_opix);
+  });
 }
 
 extern "C" void bdbnn_maxpool_bwd(const void* dy, const unsigned char* idx,
@@ -97,10 +92,9 @@ extern "C" void bdbnn_maxpool_bwd(const void* dy, const unsigned char* idx,
   PoolParams p{N, C, H, W, Ho, Wo, ks, stride, pad};
   int64_t n_ipix = (int64_t)N * H * W;
   int grid = grid_pix8(n_ipix, C);
-  if (bf16)
-    maxpool_bwd_kernel<uint16_t><<<grid, 256, 0, stream>>>(
-        (const uint16_t*)dy, idx, (uint16_t*)dx, p, n_ipix);
-  else
-    maxpool_bwd_kernel<float><<<grid, 256, 0, stream>>>(
-        (const float*)dy, idx, (float*)dx, p, n_ipix);
+  with_dtype(bf16, [&](auto t) {
+    using T = decltype(t);
+    maxpool_bwd_kernel<T><<<grid, 256, 0, stream>>>((const T*)dy, idx,
+                                                    (T*)dx, p, n_ipix);
+  });
 }

@@ -38,8 +38,7 @@ __global__ void prelu_bwd_kernel(const T* __restrict__ x,
                                  int C) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* da_lds = (float*)smem_raw;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) da_lds[c] = 0.f;
-  __syncthreads();
+  chan_sums_zero<1>(da_lds, C);
   ChanMap m = chan_map8(C);
   float av[8], acc[8] = {};
 #pragma unroll
@@ -56,11 +55,8 @@ __global__ void prelu_bwd_kernel(const T* __restrict__ x,
     }
     store8(dx, i, dxv);
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) atomicAdd(&da_lds[m.c0 + j], acc[j]);
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += blockDim.x)
-    if (da_lds[c] != 0.f) atomicAdd(&da[c], da_lds[c]);
+  chan_sums_add<1>(da_lds, C, m.c0, {acc});
+  chan_sums_flush<1, false>(da_lds, C, {da}, 1, 0);
 }
 
 extern "C" void bdbnn_prelu_fwd(const void* x, const float* a, void* y,
@@ -68,12 +64,11 @@ extern "C" void bdbnn_prelu_fwd(const void* x, const float* a, void* y,
                                 hipStream_t stream) {
   int64_t n_pix = n / C;
   int grid = grid_pix8(n_pix, C);
-  if (bf16)
-    prelu_fwd_kernel<uint16_t><<<grid, 256, 0, stream>>>(
-        (const uint16_t*)x, a, (uint16_t*)y, n_pix, C);
-  else
-    prelu_fwd_kernel<float><<<grid, 256, 0, stream>>>(
-        (const float*)x, a, (float*)y, n_pix, C);
+  with_dtype(bf16, [&](auto t) {
+    using T = decltype(t);
+    prelu_fwd_kernel<T><<<grid, 256, 0, stream>>>((const T*)x, a, (T*)y,
+                                                  n_pix, C);
+  });
 }
 
 extern "C" void bdbnn_prelu_bwd(const void* x, const void* g, const float* a,
@@ -83,11 +78,9 @@ extern "C" void bdbnn_prelu_bwd(const void* x, const void* g, const float* a,
   int grid = grid_pix8(n_pix, C);
   size_t lds = sizeof(float) * C;
   hipMemsetAsync(da, 0, sizeof(float) * C, stream);
-  if (bf16)
-    prelu_bwd_kernel<uint16_t><<<grid, 256, lds, stream>>>(
-        (const uint16_t*)x, (const uint16_t*)g, a, (uint16_t*)dx, da, n_pix,
-        C);
-  else
-    prelu_bwd_kernel<float><<<grid, 256, lds, stream>>>(
-        (const float*)x, (const float*)g, a, (float*)dx, da, n_pix, C);
+  with_dtype(bf16, [&](auto t) {
+    using T = decltype(t);
+    prelu_bwd_kernel<T><<<grid, 256, lds, stream>>>(
+        (const T*)x, (const T*)g, a, (T*)dx, da, n_pix, C);
+  });
 }

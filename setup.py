@@ -26,10 +26,8 @@ sources = [os.path.join(CSRC, f) for f in (
     "bn_pool.hip",
     "pool.hip",
     "loss.hip",
-    "conv_dgrad.hip",
     "conv_bwd.hip",
     "conv_bwd_s2.hip",
-    "conv_wgrad.hip",
     "stem_conv.hip",
     "xnor_conv.hip",
     "kurtosis.hip",
@@ -45,11 +43,7 @@ setup(
             sources=sources,
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],
-                # rocWMMA (conv_dgrad.hip) needs HIP half conversions,
-                # which torch's extension defaults disable
-                "nvcc": ["-O3", "-std=c++17",
-                         "-U__HIP_NO_HALF_CONVERSIONS__",
-                         "-U__HIP_NO_HALF_OPERATORS__"],
+                "nvcc": ["-O3", "-std=c++17"],
             },
         )
     ],

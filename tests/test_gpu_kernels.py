@@ -71,6 +71,131 @@ def test_ste_mask_modes():
     assert torch.allclose(out, _cl(g * 1.5 * 2.0 * (1 - th * th)), atol=1e-5)
 
 
+# ---- pack family, exact: tail word, dtype pairings, bit boundaries ----
+# Every expected value is computed with torch from the same device
+# tensors and compared with torch.equal; no tolerance is involved.
+
+# sign / clip-mask boundaries: both zeros, +-1, the next bf16 above 1 and
+# below -1 (1 + 2^-7, exact in fp32 too), and inf
+_PACK_PROBES = [0.0, -0.0, 1.0, -1.0, 1.0078125, -1.0078125, float("inf")]
+_PACK_DTYPES = [torch.float32, torch.bfloat16]
+
+
+def _pack_input(C, dtype):
+    """(2, C, 3, 5) channels_last, random * 2, with the probes written into
+    the first word of pixel (0, 0, 0) and the last word of pixel (1, 2, 4):
+    the tail word and a full word at C = 48, the (only) tail word at
+    C = 8, full words at C = 64."""
+    gen = torch.Generator(device="cuda").manual_seed(100 + C)
+    x = (torch.randn(2, C, 3, 5, device="cuda", generator=gen) * 2).to(dtype)
+    probes = torch.tensor(_PACK_PROBES, device="cuda", dtype=dtype)
+    x[0, :len(_PACK_PROBES), 0, 0] = probes
+    x[1, C - 8:C - 8 + len(_PACK_PROBES), 2, 4] = probes
+    return _cl(x)
+
+
+def _words_from_bools(b):
+    """bool (N, C, H, W) -> int64 (N, H, W, CW) words, bit c%32 of word
+    c//32 = b[:, c]; bits past C are 0."""
+    N, C, H, W = b.shape
+    CW = (C + 31) // 32
+    nhwc = b.permute(0, 2, 3, 1).to(torch.int64)
+    nhwc = F.pad(nhwc, (0, 32 * CW - C)).reshape(N, H, W, CW, 32)
+    weights = 2 ** torch.arange(32, device=b.device, dtype=torch.int64)
+    return (nhwc * weights).sum(-1)
+
+
+def _bools_from_words(words, C):
+    """int32 (N, H, W, CW) words -> bool (N, C, H, W)"""
+    w = words.to(torch.int64) & 0xFFFFFFFF
+    sh = torch.arange(32, device=words.device, dtype=torch.int64)
+    bits = ((w.unsqueeze(-1) >> sh) & 1).flatten(3)[..., :C]
+    return bits.permute(0, 3, 1, 2).bool()
+
+
+def _u32(words):
+    return words.to(torch.int64) & 0xFFFFFFFF
+
+
+@pytest.mark.parametrize("dtype", _PACK_DTYPES, ids=["fp32", "bf16"])
+@pytest.mark.parametrize("C", [8, 48, 64])
+def test_sign_and_mask_pack_exact(C, dtype):
+    nat = _nat()
+    x = _pack_input(C, dtype)
+    sp1 = nat.sign_pack_nhwc(x)
+    sp2, mp = nat.sign_mask_pack_nhwc(x)
+    CW = (C + 31) // 32
+    assert sp1.shape == sp2.shape == mp.shape == (2, 3, 5, CW)
+    assert torch.equal(_u32(sp1), _words_from_bools(x >= 0))
+    assert torch.equal(_u32(mp), _words_from_bools(x.abs() <= 1))
+    assert torch.equal(sp1, sp2)
+    if C % 32:   # unused tail bits are 0 in both planes
+        for plane in (sp1, sp2, mp):
+            assert (_u32(plane)[..., -1] >> (C % 32) == 0).all()
+    # the probes really sit where the docstring of _pack_input says
+    sign = _bools_from_words(sp2, C)
+    clip = _bools_from_words(mp, C)
+    for n, c0, h, w in [(0, 0, 0, 0), (1, C - 8, 2, 4)]:
+        assert sign[n, c0:c0 + 7, h, w].tolist() == [
+            True, True, True, False, True, False, True]
+        assert clip[n, c0:c0 + 7, h, w].tolist() == [
+            True, True, True, True, False, False, False]
+
+
+@pytest.mark.parametrize("out_bf16", [False, True], ids=["fp32", "bf16"])
+def test_decode_packed_exact_tail_word(out_bf16):
+    C = 48
+    nat = _nat()
+    sp = nat.sign_pack_nhwc(_pack_input(C, torch.float32))
+    y = nat.decode_packed(sp, C, out_bf16)
+    dt = torch.bfloat16 if out_bf16 else torch.float32
+    assert y.shape == (2, C, 3, 5) and y.dtype == dt
+    one = torch.ones((), device="cuda", dtype=dt)
+    assert torch.equal(y, torch.where(_bools_from_words(sp, C), one, -one))
+
+
+@pytest.mark.parametrize("out_dtype", _PACK_DTYPES, ids=["out_fp32",
+                                                         "out_bf16"])
+@pytest.mark.parametrize("g_dtype", _PACK_DTYPES, ids=["g_fp32", "g_bf16"])
+def test_mask_mul_packed_exact_all_dtype_pairs(g_dtype, out_dtype):
+    C = 48
+    nat = _nat()
+    _, mp = nat.sign_mask_pack_nhwc(_pack_input(C, torch.float32))
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    g = _cl(torch.randn(2, C, 3, 5, device="cuda",
+                        generator=gen).to(g_dtype))
+    dx = nat.mask_mul_packed(g, mp, C, out_dtype == torch.bfloat16)
+    assert dx.shape == g.shape and dx.dtype == out_dtype
+    want = torch.where(_bools_from_words(mp, C), g.float(),
+                       torch.zeros((), device="cuda")).to(out_dtype)
+    assert torch.equal(dx, want)
+
+
+@pytest.mark.parametrize("g_dtype", _PACK_DTYPES, ids=["g_fp32", "g_bf16"])
+@pytest.mark.parametrize("x_dtype", _PACK_DTYPES, ids=["x_fp32", "x_bf16"])
+def test_ste_mask_mul_react_polynomial_exact_at_probes(x_dtype, g_dtype):
+    """ste_mask_mul mode 1 and conv_dgrad2_x mode 1 apply one
+    react_poly_mask; on a unit gradient the former is the polynomial
+    itself, exact at the boundary probes of tests/test_gpu_bwd_modes.py
+    (2 * x is exact, so 2 +- 2x rounds once, as torch's does)."""
+    from test_gpu_bwd_modes import EDGE
+    gen = torch.Generator(device="cuda").manual_seed(11)
+    x = torch.randn(2, 16, 3, 5, device="cuda", generator=gen).to(x_dtype)
+    x[0, :len(EDGE), 0, 0] = torch.tensor(EDGE, device="cuda", dtype=x_dtype)
+    x = _cl(x)
+    ones = _cl(torch.ones(2, 16, 3, 5, device="cuda", dtype=g_dtype))
+    out = _nat().ste_mask_mul(ones, x, 1, 0.0, 0.0)
+    xf = x.float()
+    poly = torch.where((xf >= -1) & (xf < 0), 2 + 2 * xf,
+                       torch.where((xf >= 0) & (xf < 1), 2 - 2 * xf,
+                                   torch.zeros_like(xf))).to(x_dtype)
+    assert out.dtype == x_dtype
+    assert torch.equal(out[0, :len(EDGE), 0, 0], poly[0, :len(EDGE), 0, 0])
+    assert out[0, :len(EDGE), 0, 0].tolist() == [
+        0.0, 2.0, 2.0, 0.0, 1.0, 1.0, 0.0, 0.0]
+    assert torch.equal(out, poly)
+
+
 # ---------------- xnor conv ----------------
 
 @pytest.mark.parametrize("shape", [
@@ -571,74 +696,6 @@ def test_model_eval_gpu_matches_cpu():
         out_c = m_cpu(x)
     assert torch.allclose(out_g.cpu(), out_c, atol=2e-2, rtol=1e-2), \
         (out_g.cpu() - out_c).abs().max().item()
-
-
-# ---------------- experimental MFMA dgrad (round-2 seed) ----------------
-
-import os as _os
-
-
-def test_experimental_conv_dgrad_matches_reference():
-    # validated on MI355X (first-shot numerics pass); default-off in the
-    # training path until round-2 perf tuning
-    torch.manual_seed(23)
-    nat = _nat()
-    for (N, C, H, K) in [(2, 64, 8, 64), (1, 128, 16, 32)]:
-        g = torch.randn(N, K, H, H, device="cuda", dtype=torch.bfloat16)
-        g = _cl(g)
-        w = torch.randn(K, C, 3, 3, device="cuda")
-        wp, alpha, stab = nat.weight_pack(w)
-        if (N * H * H) % 128 or C % 64 or K % 16:
-            continue
-        dx = nat.conv_dgrad(g, wp, alpha, C)
-        wb = (weight_scale(w) * binsign(w)).to(torch.bfloat16)
-        ref = torch.nn.functional.conv_transpose2d(
-            g.float(), wb.float(), None, stride=1, padding=1)
-        assert dx.shape == ref.shape
-        assert torch.allclose(dx.float(), _cl(ref), atol=0.5, rtol=2e-2), \
-            (dx.float() - _cl(ref)).abs().max().item()
-
-
-def test_dgrad_v1_v2_cross_check():
-    """The two independent MFMA dgrad implementations (v1 rocWMMA
-    in-kernel decode, v2 halo implicit GEMM) must agree: v2's fused
-    mask == mask_mul(v1)."""
-    torch.manual_seed(25)
-    nat = _nat()
-    N, C, H, K = 2, 64, 56, 64
-    g = _cl(torch.randn(N, K, H, H, device="cuda", dtype=torch.bfloat16))
-    w = torch.randn(K, C, 3, 3, device="cuda")
-    x = torch.randn(N, C, H, H, device="cuda")
-    wp, alpha, _ = nat.weight_pack(w)
-    _, mp = nat.sign_mask_pack_nhwc(_cl(x))
-    wd = nat.dgrad_weight_decode(wp, alpha, C)
-    dx2 = nat.conv_dgrad2(g, wd, mp, C)
-    dx1 = nat.mask_mul_packed(nat.conv_dgrad(g, wp, alpha, C), mp, C, True)
-    assert torch.allclose(dx2.float(), dx1.float(), atol=5e-2,
-                          rtol=2e-2), (dx2.float() -
-                                       dx1.float()).abs().max().item()
-
-
-def test_experimental_conv_wgrad_matches_reference():
-    # validated on MI355X (first-shot numerics pass); default-off in the
-    # training path until round-2 perf tuning
-    torch.manual_seed(24)
-    nat = _nat()
-    for (N, C, H, K) in [(2, 32, 8, 32), (1, 64, 16, 64)]:
-        x = torch.randn(N, C, H, H, device="cuda")
-        g = _cl(torch.randn(N, K, H, H, device="cuda",
-                            dtype=torch.bfloat16))
-        xp = nat.sign_pack_nhwc(_cl(x))
-        dw = nat.conv_wgrad(g, xp, C)
-        xb = binsign(x).to(torch.bfloat16)
-        ref = torch.ops.aten.convolution_backward(
-            g.float(), xb.float(),
-            torch.empty(K, C, 3, 3, device="cuda"), None,
-            [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-            [False, True, False])[1]
-        assert dw.shape == ref.shape
-        assert torch.allclose(dw, ref, atol=0.5, rtol=2e-2), \
-            (dw - ref).abs().max().item()
 
 
 def test_vgg_small_gpu_step():
