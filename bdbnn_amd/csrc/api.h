@@ -23,6 +23,14 @@ struct PtrList { float* ptr[BDBNN_MAX_TENSORS]; };
 // (block -> tensor, offset) is built with the same constant.
 constexpr int64_t BDBNN_CHUNK_ELEMS = 32 * 1024;
 
+// Rows of the fused BN backward's per-channel sums ([C][rows]; the sliced
+// partials are [32][C][rows]): sum dz, sum dz*xhat, da, and for RPReLU
+// (act_kind 3) sum dy.  The bn_act.hip kernels, their launchers and the
+// allocations in bind.cpp all size by this.
+constexpr int bdbnn_bn_sum_rows(int act_kind) {
+  return act_kind == 3 ? 4 : 3;
+}
+
 extern "C" {
 
 // ---- pack.hip ----
@@ -96,6 +104,8 @@ void bdbnn_prelu_bwd(const void* x, const void* g, const float* a, void* dx,
                      hipStream_t stream);
 
 // ---- bn_act.hip ----
+// act_kind: 0 identity, 1 PReLU (a), 2 ReLU, 3 RPReLU (a, b1, b2); sums32 /
+// sums hold bdbnn_bn_sum_rows(act_kind) rows per channel
 void bdbnn_bn_stats(const void* x, float* s1, float* s2, int64_t n, int C,
                     bool bf16, hipStream_t stream);
 void bdbnn_bn_finalize(const float* s1, const float* s2, float* mean,
@@ -104,10 +114,10 @@ void bdbnn_bn_finalize(const float* s1, const float* s2, float* mean,
                        float eps, int nslice, hipStream_t stream);
 void bdbnn_bn_act_fwd(const void* x, const void* skip, const float* mean,
                       const float* invstd, const float* gamma,
-                      const float* beta, const float* a, void* out,
-                      void* zout, int64_t n, int C, int act_kind,
-                      uint32_t* xpk, uint32_t* mpk, bool bf16,
-                      hipStream_t stream);
+                      const float* beta, const float* a, const float* b1,
+                      const float* b2, void* out, void* zout, int64_t n,
+                      int C, int act_kind, uint32_t* xpk, uint32_t* mpk,
+                      bool bf16, hipStream_t stream);
 void bdbnn_bn_act_bwd_reduce(const void* dy, const void* z, const void* x,
                              const float* mean, const float* invstd,
                              const float* a, float* sums32, float* sums,
@@ -124,8 +134,9 @@ void bdbnn_bn_act_bwd_apply(const void* dy, const void* z, const void* x,
                             bool bf16, hipStream_t stream);
 void bdbnn_bn_act_eval(const void* x, const void* skip, const float* rm,
                        const float* rv, const float* gamma,
-                       const float* beta, const float* a, void* out,
-                       int64_t n, int C, int act_kind, float eps, bool bf16,
+                       const float* beta, const float* a, const float* b1,
+                       const float* b2, void* out, int64_t n, int C,
+                       int act_kind, float eps, bool bf16,
                        hipStream_t stream);
 
 // ---- bn_pool.hip ----

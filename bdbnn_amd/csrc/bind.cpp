@@ -597,6 +597,23 @@ std::vector<at::Tensor> prelu_bwd(const at::Tensor& g, const at::Tensor& x,
 
 // ---------------- fused BN (+add) (+act) ----------------
 
+// RPReLU (act_kind 3) reads a, b1 and b2 per channel: all three present,
+// on the device, C elements each.  The other kinds take no shifts.
+static void check_rprelu_args(int64_t act_kind, int64_t C,
+                              const c10::optional<at::Tensor>& a,
+                              const c10::optional<at::Tensor>& b1,
+                              const c10::optional<at::Tensor>& b2,
+                              const char* who) {
+  if (act_kind != 3) return;
+  const c10::optional<at::Tensor>* ts[3] = {&a, &b1, &b2};
+  const char* names[3] = {"a", "b1", "b2"};
+  for (int i = 0; i < 3; ++i) {
+    TORCH_CHECK(ts[i]->has_value(), who, ": RPReLU needs ", names[i]);
+    TORCH_CHECK((*ts[i])->is_cuda() && (*ts[i])->numel() == C, who, ": ",
+                names[i], " must be a CUDA tensor of C elements");
+  }
+}
+
 std::vector<at::Tensor> bn_act_fwd_train(
     const at::Tensor& x, const c10::optional<at::Tensor>& skip,
     const at::Tensor& gamma, const at::Tensor& beta,
@@ -604,10 +621,13 @@ std::vector<at::Tensor> bn_act_fwd_train(
     c10::optional<at::Tensor> running_mean,
     c10::optional<at::Tensor> running_var, double momentum, double eps,
     int64_t act_kind, const c10::optional<at::Tensor>& pre_s1,
-    const c10::optional<at::Tensor>& pre_s2, bool want_pack) {
+    const c10::optional<at::Tensor>& pre_s2, bool want_pack,
+    const c10::optional<at::Tensor>& b1,
+    const c10::optional<at::Tensor>& b2) {
   check_vec8(x, true, "x", "bn_act_fwd_train");
   auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
   int C = (int)x.size(1);
+  check_rprelu_args(act_kind, C, a, b1, b2, "bn_act_fwd_train");
   TORCH_CHECK(gamma.numel() == C && beta.numel() == C &&
                   (!a.has_value() || a->numel() == C),
               "bn_act_fwd_train: gamma, beta and a must have C elements");
@@ -619,11 +639,13 @@ std::vector<at::Tensor> bn_act_fwd_train(
       bn_train_stats(xc, C, pre_s1, pre_s2, running_mean, running_var,
                      momentum, eps, "bn_act_fwd_train");
   auto out = at::empty_like(xc, xc.options(), at::MemoryFormat::ChannelsLast);
-  // PReLU backward needs the true pre-activation z; ReLU only needs its
-  // sign (recoverable from out) and identity ignores it — skip the write.
+  // PReLU backward needs the true pre-activation z (RPReLU: the shifted
+  // u = z + b1, which is what the kernel stores for it); ReLU only needs
+  // its sign (recoverable from out) and identity ignores it — skip the
+  // write.
   at::Tensor z;
   void* zptr = nullptr;
-  if (act_kind == 1) {
+  if (act_kind == 1 || act_kind == 3) {
     z = at::empty_like(xc, xc.options(), at::MemoryFormat::ChannelsLast);
     zptr = z.data_ptr();
   } else {
@@ -635,6 +657,9 @@ std::vector<at::Tensor> bn_act_fwd_train(
   auto bf = chan_f32(beta);
   at::Tensor af;
   const float* a_ptr = opt_chan_ptr(a, af);
+  at::Tensor b1f, b2f;
+  const float* b1_ptr = act_kind == 3 ? opt_chan_ptr(b1, b1f) : nullptr;
+  const float* b2_ptr = act_kind == 3 ? opt_chan_ptr(b2, b2f) : nullptr;
   // consumer-conv sign/mask pack fused into the epilogue (the next
   // binary conv then skips its own pack read pass; csrc/bn_act.hip)
   at::Tensor xpk, mpk;
@@ -650,8 +675,9 @@ std::vector<at::Tensor> bn_act_fwd_train(
   }
   bdbnn_bn_act_fwd(xc.data_ptr(), skip_ptr, mean.data_ptr<float>(),
                    invstd.data_ptr<float>(), gf.data_ptr<float>(),
-                   bf.data_ptr<float>(), a_ptr, out.data_ptr(), zptr,
-                   n, C, (int)act_kind, xpk_p, mpk_p, bf16, cur_stream());
+                   bf.data_ptr<float>(), a_ptr, b1_ptr, b2_ptr,
+                   out.data_ptr(), zptr, n, C, (int)act_kind, xpk_p, mpk_p,
+                   bf16, cur_stream());
   if (want_pack) return {out, z, mean, invstd, xpk, mpk};
   return {out, z, mean, invstd};
 }
@@ -672,8 +698,9 @@ std::vector<at::Tensor> bn_act_bwd(
                   gamma.numel() == x.size(1) &&
                   (!a.has_value() || a->numel() == x.size(1)),
               "bn_act_bwd: mean, invstd, gamma and a must have C elements");
-  TORCH_CHECK(act_kind != 1 || a.has_value(),
-              "bn_act_bwd: PReLU needs its slopes a");
+  // RPReLU's backward reads a alone: the shifts are in the saved plane
+  TORCH_CHECK((act_kind != 1 && act_kind != 3) || a.has_value(),
+              "bn_act_bwd: PReLU and RPReLU need their slopes a");
   auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
   auto zc = z.contiguous(at::MemoryFormat::ChannelsLast);
   auto dyc = dy.to(xc.scalar_type()).contiguous(at::MemoryFormat::ChannelsLast);
@@ -681,8 +708,9 @@ std::vector<at::Tensor> bn_act_bwd(
   int64_t n = xc.numel();
   bool bf16 = is_bf16(xc);
   auto fopt = xc.options().dtype(at::kFloat);
-  auto sums32 = at::empty({32, C, 3}, fopt);  // sliced partials
-  auto sums = at::empty({C, 3}, fopt);
+  const int NR = bdbnn_bn_sum_rows((int)act_kind);
+  auto sums32 = at::empty({32, C, NR}, fopt);  // sliced partials
+  auto sums = at::empty({C, NR}, fopt);
   at::Tensor af;
   const float* a_ptr = opt_chan_ptr(a, af);
   bdbnn_bn_act_bwd_reduce(dyc.data_ptr(), zc.data_ptr(), xc.data_ptr(),
@@ -708,6 +736,11 @@ std::vector<at::Tensor> bn_act_bwd(
   auto dbeta = sums.select(1, 0).clone();
   auto dgamma = sums.select(1, 1).clone();
   auto da = sums.select(1, 2).clone();
+  if (act_kind == 3) {
+    // db1 = sum dz, the number dbeta is; db2 = sum dy
+    return {dx, dskip, dgamma, dbeta, da, dbeta.clone(),
+            sums.select(1, 3).clone()};
+  }
   return {dx, dskip, dgamma, dbeta, da};
 }
 
@@ -716,8 +749,11 @@ at::Tensor bn_act_eval(const at::Tensor& x,
                        const at::Tensor& gamma, const at::Tensor& beta,
                        const c10::optional<at::Tensor>& a,
                        const at::Tensor& rm, const at::Tensor& rv,
-                       double eps, int64_t act_kind) {
+                       double eps, int64_t act_kind,
+                       const c10::optional<at::Tensor>& b1,
+                       const c10::optional<at::Tensor>& b2) {
   check_vec8(x, true, "x", "bn_act_eval");
+  check_rprelu_args(act_kind, x.size(1), a, b1, b2, "bn_act_eval");
   TORCH_CHECK(gamma.numel() == x.size(1) && beta.numel() == x.size(1) &&
                   rm.numel() == x.size(1) && rv.numel() == x.size(1) &&
                   (!a.has_value() || a->numel() == x.size(1)),
@@ -737,10 +773,14 @@ at::Tensor bn_act_eval(const at::Tensor& x,
   auto rvf = chan_f32(rv);
   at::Tensor af;
   const float* a_ptr = opt_chan_ptr(a, af);
+  at::Tensor b1f, b2f;
+  const float* b1_ptr = act_kind == 3 ? opt_chan_ptr(b1, b1f) : nullptr;
+  const float* b2_ptr = act_kind == 3 ? opt_chan_ptr(b2, b2f) : nullptr;
   bdbnn_bn_act_eval(xc.data_ptr(), skip_ptr, rmf.data_ptr<float>(),
                     rvf.data_ptr<float>(), gf.data_ptr<float>(),
-                    bf.data_ptr<float>(), a_ptr, out.data_ptr(), n, C,
-                    (int)act_kind, (float)eps, bf16, cur_stream());
+                    bf.data_ptr<float>(), a_ptr, b1_ptr, b2_ptr,
+                    out.data_ptr(), n, C, (int)act_kind, (float)eps, bf16,
+                    cur_stream());
   return out;
 }
 
@@ -1326,9 +1366,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("prelu_fwd", &prelu_fwd, "fused NHWC per-channel PReLU fwd");
   m.def("prelu_bwd", &prelu_bwd, "fused NHWC per-channel PReLU bwd");
   m.def("bn_act_fwd_train", &bn_act_fwd_train,
-        "fused BN(+add)(+act) training forward");
-  m.def("bn_act_bwd", &bn_act_bwd, "fused BN(+add)(+act) backward");
-  m.def("bn_act_eval", &bn_act_eval, "fused BN(+add)(+act) eval forward");
+        "fused BN(+add)(+act) training forward -> [out, z, mean, invstd(, "
+        "xpk, mpk)]; act_kind 3 (RPReLU) takes b1, b2 and stores u = z + b1 "
+        "as z",
+        py::arg("x"), py::arg("skip"), py::arg("gamma"), py::arg("beta"),
+        py::arg("a"), py::arg("running_mean"), py::arg("running_var"),
+        py::arg("momentum"), py::arg("eps"), py::arg("act_kind"),
+        py::arg("pre_s1"), py::arg("pre_s2"), py::arg("want_pack"),
+        py::arg("b1") = py::none(), py::arg("b2") = py::none());
+  m.def("bn_act_bwd", &bn_act_bwd,
+        "fused BN(+add)(+act) backward -> [dx, dskip, dgamma, dbeta, da]; "
+        "act_kind 3 appends db1, db2");
+  m.def("bn_act_eval", &bn_act_eval, "fused BN(+add)(+act) eval forward",
+        py::arg("x"), py::arg("skip"), py::arg("gamma"), py::arg("beta"),
+        py::arg("a"), py::arg("rm"), py::arg("rv"), py::arg("eps"),
+        py::arg("act_kind"), py::arg("b1") = py::none(),
+        py::arg("b2") = py::none());
   m.def("bn_relu_maxpool_fwd_train", &bn_relu_maxpool_fwd_train,
         "fused BN + ReLU + maxpool training forward -> [out, idx, mean, "
         "invstd(, xpk, mpk)]",

@@ -14,7 +14,13 @@
 //
 // BN semantics match nn.BatchNorm2d: biased batch var for normalization,
 // unbiased var into running_var, momentum update in the finalize step.
-// act_kind: 0 = identity, 1 = per-channel PReLU, 2 = ReLU.
+// act_kind: 0 = identity, 1 = per-channel PReLU, 2 = ReLU,
+// 3 = RPReLU (ReActNet): u = z + b1, out = PReLU_a(u) + b2, with the two
+// per-channel fp32 shifts b1 / b2.  The plane saved for backward holds u
+// (rounded to the storage type), never z: backward needs the branch u > 0
+// and, for da, the value of u, and rounding keeps the sign of u, so both
+// directions take the same branch.  u recomputed from a rounded z + b1
+// would not.
 #include "common.h"
 #include "vec8.h"
 #include "bn_affine.h"
@@ -102,17 +108,23 @@ __global__ void bn_act_fwd_kernel(const T* __restrict__ x,
                                   const float* __restrict__ gamma,
                                   const float* __restrict__ beta,
                                   const float* __restrict__ a,
+                                  const float* __restrict__ b1,
+                                  const float* __restrict__ b2,
                                   T* __restrict__ out, T* __restrict__ zout,
                                   int64_t n_pix, int C,
                                   uint32_t* __restrict__ xpk,
                                   uint32_t* __restrict__ mpk) {
   ChanMap m = chan_map8(C);
-  float sc[8], sh[8], av[8];
+  float sc[8], sh[8], av[8], b2v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     int cc = m.c0 + j;
     bn_scale_shift(gamma[cc], beta[cc], mean[cc], invstd[cc], sc[j], sh[j]);
-    av[j] = (ACT == 1) ? a[cc] : 0.f;
+    av[j] = (ACT == 1 || ACT == 3) ? a[cc] : 0.f;
+    // RPReLU: the first shift rides in the affine's constant, so z below
+    // is u = BN(x) + b1 (+ skip) at no register or instruction cost
+    if (ACT == 3) sh[j] += b1[cc];
+    b2v[j] = (ACT == 3) ? b2[cc] : 0.f;
   }
   const int sub = threadIdx.x & 3;       // byte slot within the word
   const int64_t cw = m.c0 >> 5;            // word column (lane sub == 0)
@@ -129,6 +141,7 @@ __global__ void bn_act_fwd_kernel(const T* __restrict__ x,
       o[j] = z[j];
       if (ACT == 1) o[j] = z[j] > 0.f ? z[j] : av[j] * z[j];
       else if (ACT == 2) o[j] = bn_relu(z[j]);
+      else if (ACT == 3) o[j] = (z[j] > 0.f ? z[j] : av[j] * z[j]) + b2v[j];
     }
     store8(out, i, o);
     if (zout != nullptr) store8(zout, i, z);
@@ -142,10 +155,12 @@ __global__ void bn_act_fwd_kernel(const T* __restrict__ x,
 }
 
 // ---- backward pass 1: per-channel reductions ----
-// sums layout: [32 slices][C][3] = (sum dz, sum dz*xhat, da) partials —
-// 32-way sliced so the end-of-kernel global atomics see 1/32 of the
-// per-word contention (2048 blocks onto 3C words measured as a >20 us
-// serial tail); bn_fold_sums_kernel folds the slices.
+// sums layout: [32 slices][C][NR] = (sum dz, sum dz*xhat, da) partials,
+// NR = bdbnn_bn_sum_rows(ACT) (api.h): RPReLU adds a fourth row, sum dy
+// (= db2; db1 is sum dz, the same number as dbeta).  32-way sliced so the
+// end-of-kernel global atomics see 1/32 of the per-word contention (2048
+// blocks onto 3C words measured as a >20 us serial tail);
+// bn_fold_sums_kernel folds the slices.
 template <typename T, int ACT>
 __global__ void bn_act_bwd_reduce_kernel(
     const T* __restrict__ dy, const T* __restrict__ z,
@@ -153,17 +168,18 @@ __global__ void bn_act_bwd_reduce_kernel(
     const float* __restrict__ invstd, const float* __restrict__ a,
     float* __restrict__ sums, int64_t n_pix, int C) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* lds = (float*)smem_raw;   // [3][C]
-  chan_sums_zero<3>(lds, C);
+  constexpr int NR = bdbnn_bn_sum_rows(ACT);
+  float* lds = (float*)smem_raw;   // [NR][C]
+  chan_sums_zero<NR>(lds, C);
   ChanMap m = chan_map8(C);
   float mu[8], is[8], av[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     int cc = m.c0 + j;
     mu[j] = mean[cc]; is[j] = invstd[cc];
-    av[j] = (ACT == 1) ? a[cc] : 0.f;
+    av[j] = (ACT == 1 || ACT == 3) ? a[cc] : 0.f;
   }
-  float s0[8] = {}, s1[8] = {}, s2[8] = {};
+  float s0[8] = {}, s1[8] = {}, s2[8] = {}, s3[8] = {};
   // 2 pixel iterations in flight (6 independent loads): one blocking
   // triple per iteration leaves the wave latency-bound.  (The r1
   // attempt unrolled with a COMBINED body and regressed on register
@@ -175,9 +191,10 @@ __global__ void bn_act_bwd_reduce_kernel(
     _Pragma("unroll")                                                     \
     for (int j = 0; j < 8; ++j) {                                         \
       float dz = DYV[j];                                                  \
-      if (ACT == 1) {                                                     \
+      if (ACT == 1 || ACT == 3) {                                         \
         dz = ZV[j] > 0.f ? DYV[j] : av[j] * DYV[j];                       \
         if (ZV[j] <= 0.f) s2[j] += DYV[j] * ZV[j];                        \
+        if (ACT == 3) s3[j] += DYV[j];                                    \
       } else if (ACT == 2) {                                              \
         dz = ZV[j] > 0.f ? DYV[j] : 0.f;                                  \
       }                                                                   \
@@ -207,13 +224,20 @@ __global__ void bn_act_bwd_reduce_kernel(
     BN_RED_BODY(dyv, zv, xv)
   }
 #undef BN_RED_BODY
-  // da (row 2) is PReLU's only; the row stays zero and is skipped otherwise
-  if (ACT == 1) chan_sums_add<3>(lds, C, m.c0, {s0, s1, s2});
-  else          chan_sums_add<2>(lds, C, m.c0, {s0, s1});
-  chan_sums_flush<3, true>(lds, C, {sums, sums + 1, sums + 2}, 3, C * 3);
+  // da (row 2) is PReLU's and RPReLU's only; the row stays zero and is
+  // skipped otherwise.  Row 3 (sum dy) exists for RPReLU alone.
+  if constexpr (ACT == 3) {
+    chan_sums_add<4>(lds, C, m.c0, {s0, s1, s2, s3});
+    chan_sums_flush<4, true>(lds, C, {sums, sums + 1, sums + 2, sums + 3},
+                             NR, C * NR);
+  } else {
+    if (ACT == 1) chan_sums_add<3>(lds, C, m.c0, {s0, s1, s2});
+    else          chan_sums_add<2>(lds, C, m.c0, {s0, s1});
+    chan_sums_flush<3, true>(lds, C, {sums, sums + 1, sums + 2}, NR, C * NR);
+  }
 }
 
-// fold the 32 slices -> [C][3] (tiny; launched right after the reduce)
+// fold the 32 slices -> [C][NR] (tiny; launched right after the reduce)
 __global__ void bn_fold_sums_kernel(const float* __restrict__ sums32,
                                     float* __restrict__ out, int n) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -233,6 +257,7 @@ __global__ void bn_act_bwd_apply_kernel(
     const float* __restrict__ a, const float* __restrict__ sums,
     T* __restrict__ dx, T* __restrict__ dskip, int64_t n_pix, int C,
     float inv_n) {
+  constexpr int NR = bdbnn_bn_sum_rows(ACT);
   ChanMap m = chan_map8(C);
   float mu[8], is[8], gis[8], av[8], sdz_n[8], sdzx_n[8];
 #pragma unroll
@@ -240,9 +265,9 @@ __global__ void bn_act_bwd_apply_kernel(
     int cc = m.c0 + j;
     mu[j] = mean[cc]; is[j] = invstd[cc];
     gis[j] = gamma[cc] * is[j];
-    av[j] = (ACT == 1) ? a[cc] : 0.f;
-    sdz_n[j] = sums[cc * 3 + 0] * inv_n;
-    sdzx_n[j] = sums[cc * 3 + 1] * inv_n;
+    av[j] = (ACT == 1 || ACT == 3) ? a[cc] : 0.f;
+    sdz_n[j] = sums[cc * NR + 0] * inv_n;
+    sdzx_n[j] = sums[cc * NR + 1] * inv_n;
   }
   // 2 pixel iterations in flight (up to 6 independent loads): one
   // blocking triple per iteration leaves the wave latency-bound
@@ -253,7 +278,8 @@ __global__ void bn_act_bwd_apply_kernel(
     _Pragma("unroll")                                                     \
     for (int j = 0; j < 8; ++j) {                                         \
       float dz = DYV[j];                                                  \
-      if (ACT == 1) dz = ZV[j] > 0.f ? DYV[j] : av[j] * DYV[j];           \
+      if (ACT == 1 || ACT == 3)                                           \
+        dz = ZV[j] > 0.f ? DYV[j] : av[j] * DYV[j];                       \
       else if (ACT == 2) dz = ZV[j] > 0.f ? DYV[j] : 0.f;                 \
       float xhat = (XV[j] - mu[j]) * is[j];                               \
       dxv[j] = gis[j] * (dz - sdz_n[j] - xhat * sdzx_n[j]);               \
@@ -294,17 +320,21 @@ __global__ void bn_act_eval_kernel(const T* __restrict__ x,
                                    const float* __restrict__ gamma,
                                    const float* __restrict__ beta,
                                    const float* __restrict__ a,
+                                   const float* __restrict__ b1,
+                                   const float* __restrict__ b2,
                                    T* __restrict__ out, int64_t n_pix, int C,
                                    float eps) {
   ChanMap m = chan_map8(C);
-  float sc[8], sh[8], av[8];
+  float sc[8], sh[8], av[8], b2v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     int cc = m.c0 + j;
     float is = rsqrtf(rv[cc] + eps);
     sc[j] = gamma[cc] * is;
     sh[j] = beta[cc] - rm[cc] * sc[j];
-    av[j] = (ACT == 1) ? a[cc] : 0.f;
+    av[j] = (ACT == 1 || ACT == 3) ? a[cc] : 0.f;
+    if (ACT == 3) sh[j] += b1[cc];   // as in bn_act_fwd_kernel
+    b2v[j] = (ACT == 3) ? b2[cc] : 0.f;
   }
   float v[8], s[8], o[8];
   for (int64_t p = m.p0; p < n_pix; p += m.pstep) {
@@ -318,6 +348,7 @@ __global__ void bn_act_eval_kernel(const T* __restrict__ x,
       o[j] = zv;
       if (ACT == 1) o[j] = zv > 0.f ? zv : av[j] * zv;
       else if (ACT == 2) o[j] = fmaxf(zv, 0.f);
+      else if (ACT == 3) o[j] = (zv > 0.f ? zv : av[j] * zv) + b2v[j];
     }
     store8(out, i, o);
   }
@@ -353,20 +384,22 @@ extern "C" void bdbnn_bn_finalize(const float* s1, const float* s2,
 extern "C" void bdbnn_bn_act_fwd(const void* x, const void* skip,
                                  const float* mean, const float* invstd,
                                  const float* gamma, const float* beta,
-                                 const float* a, void* out, void* zout,
+                                 const float* a, const float* b1,
+                                 const float* b2, void* out, void* zout,
                                  int64_t n, int C, int act_kind,
                                  uint32_t* xpk, uint32_t* mpk, bool bf16,
                                  hipStream_t stream) {
   int64_t n_pix = n / C;
   int grid = grid_pix8(n_pix, C);
   with_dtype(bf16, [&](auto t) {
-    with_int<1, 2, 0>(act_kind, [&](auto act) {
+    with_int<1, 2, 3, 0>(act_kind, [&](auto act) {
       with_bool(xpk != nullptr, [&](auto pack) {
         using T = decltype(t);
         bn_act_fwd_kernel<T, decltype(act)::value, decltype(pack)::value>
             <<<grid, 256, 0, stream>>>((const T*)x, (const T*)skip, mean,
-                                       invstd, gamma, beta, a, (T*)out,
-                                       (T*)zout, n_pix, C, xpk, mpk);
+                                       invstd, gamma, beta, a, b1, b2,
+                                       (T*)out, (T*)zout, n_pix, C, xpk,
+                                       mpk);
       });
     });
   });
@@ -378,12 +411,13 @@ extern "C" void bdbnn_bn_act_bwd_reduce(const void* dy, const void* z,
                                         float* sums32, float* sums,
                                         int64_t n, int C, int act_kind,
                                         bool bf16, hipStream_t stream) {
-  hipMemsetAsync(sums32, 0, sizeof(float) * 32 * C * 3, stream);
+  const int NR = bdbnn_bn_sum_rows(act_kind);
+  hipMemsetAsync(sums32, 0, sizeof(float) * 32 * C * NR, stream);
   int64_t n_pix = n / C;
   int grid = grid_pix8(n_pix, C);
-  size_t lds = 3 * sizeof(float) * C;
+  size_t lds = NR * sizeof(float) * C;
   with_dtype(bf16, [&](auto t) {
-    with_int<1, 2, 0>(act_kind, [&](auto act) {
+    with_int<1, 2, 3, 0>(act_kind, [&](auto act) {
       using T = decltype(t);
       bn_act_bwd_reduce_kernel<T, decltype(act)::value>
           <<<grid, 256, lds, stream>>>((const T*)dy, (const T*)z,
@@ -391,8 +425,8 @@ extern "C" void bdbnn_bn_act_bwd_reduce(const void* dy, const void* z,
                                        n_pix, C);
     });
   });
-  bn_fold_sums_kernel<<<(C * 3 + 255) / 256, 256, 0, stream>>>(sums32, sums,
-                                                               C * 3);
+  bn_fold_sums_kernel<<<(C * NR + 255) / 256, 256, 0, stream>>>(
+      sums32, sums, C * NR);
 }
 
 // the slice fold on its own, for csrc/bn_pool.hip's reduce
@@ -412,7 +446,7 @@ extern "C" void bdbnn_bn_act_bwd_apply(const void* dy, const void* z,
   int64_t n_pix = n / C;
   int grid = grid_pix8(n_pix, C);
   with_dtype(bf16, [&](auto t) {
-    with_int<1, 2, 0>(act_kind, [&](auto act) {
+    with_int<1, 2, 3, 0>(act_kind, [&](auto act) {
       using T = decltype(t);
       bn_act_bwd_apply_kernel<T, decltype(act)::value>
           <<<grid, 256, 0, stream>>>((const T*)dy, (const T*)z, (const T*)x,
@@ -425,17 +459,18 @@ extern "C" void bdbnn_bn_act_bwd_apply(const void* dy, const void* z,
 extern "C" void bdbnn_bn_act_eval(const void* x, const void* skip,
                                   const float* rm, const float* rv,
                                   const float* gamma, const float* beta,
-                                  const float* a, void* out, int64_t n,
+                                  const float* a, const float* b1,
+                                  const float* b2, void* out, int64_t n,
                                   int C, int act_kind, float eps, bool bf16,
                                   hipStream_t stream) {
   int64_t n_pix = n / C;
   int grid = grid_pix8(n_pix, C);
   with_dtype(bf16, [&](auto t) {
-    with_int<1, 2, 0>(act_kind, [&](auto act) {
+    with_int<1, 2, 3, 0>(act_kind, [&](auto act) {
       using T = decltype(t);
       bn_act_eval_kernel<T, decltype(act)::value><<<grid, 256, 0, stream>>>(
-          (const T*)x, (const T*)skip, rm, rv, gamma, beta, a, (T*)out,
-          n_pix, C, eps);
+          (const T*)x, (const T*)skip, rm, rv, gamma, beta, a, b1, b2,
+          (T*)out, n_pix, C, eps);
     });
   });
 }

@@ -24,8 +24,8 @@ import torch.nn as nn
 
 from ..ops.binary_conv import HardBinaryConv
 from ..ops.stem_conv import StemConv7x7
-from ..ops.binarize import LearnableBias
-from ..ops.activations import ChannelPReLU
+from ..ops.activations import ChannelPReLU, RPReLU  # noqa: F401 (re-export)
+from ..ops import bn_act as _bn_act
 from ..ops.bn_act import fused_bn_act, fused_bn_relu_maxpool
 from ..ops.pool import FusedMaxPool2d
 
@@ -52,17 +52,13 @@ class FusedDownsample(nn.Sequential):
         return fused_bn_act(self[0](x), self[1])
 
 
-class RPReLU(nn.Module):
-    """ReActNet RPReLU: shift -> PReLU -> shift, per channel."""
-
-    def __init__(self, channels):
-        super().__init__()
-        self.move1 = LearnableBias(channels)
-        self.prelu = ChannelPReLU(channels)
-        self.move2 = LearnableBias(channels)
-
-    def forward(self, x):
-        return self.move2(self.prelu(self.move1(x)))
+def _act_fuses_pack(act):
+    """True when fused_bn_act writes the activation's final value in its
+    epilogue, so that it can pack the consuming conv's bitplanes there: a
+    plain ChannelPReLU always, an RPReLU when BDBNN_FUSE_RPRELU is on
+    (otherwise its shifts run after the BN kernel)."""
+    return isinstance(act, ChannelPReLU) or (
+        isinstance(act, RPReLU) and _bn_act._FUSE_RPRELU)
 
 
 def _make_act(kind, channels):
@@ -138,16 +134,16 @@ class BiBasicBlock(nn.Module):
             cell1 = {} if defer else None
         o1, st1 = self.conv1.forward_with_stats(x, prepack=pk_in,
                                                 skip_cell=cell1)
-        # only a plain ChannelPReLU tail writes the exact conv2 input in
-        # its epilogue (RPReLU's shifts run after, so no pack there)
-        fuse1 = isinstance(self.act1, ChannelPReLU)
+        # only a tail fused into the BN epilogue writes the exact conv2
+        # input there (an unfused RPReLU's shifts run after: no pack)
+        fuse1 = _act_fuses_pack(self.act1)
         r1 = fused_bn_act(o1, self.bn1, self.act1, skip=identity, stats=st1,
                           pack=fuse1, defer_skip_cell=cell1)
         out, pk1 = r1 if fuse1 else (r1, None)
         cell2 = {} if defer else None
         o2, st2 = self.conv2.forward_with_stats(out, prepack=pk1,
                                                 skip_cell=cell2)
-        fuse2 = isinstance(self.act2, ChannelPReLU)
+        fuse2 = _act_fuses_pack(self.act2)
         r2 = fused_bn_act(o2, self.bn2, self.act2, skip=out, stats=st2,
                           pack=fuse2, defer_skip_cell=cell2)
         out, pk2 = r2 if fuse2 else (r2, None)

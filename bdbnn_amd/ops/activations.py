@@ -4,6 +4,10 @@ training step on MI355X (profiles/r01_bench_b256_kernel_stats.md); the
 HIP kernel (csrc/prelu.hip) is one memory-bound pass each way.
 
 State-dict compatible with nn.PReLU (same parameter name/shape).
+
+RPReLU (ReActNet: shift -> PReLU -> shift) is the composition of three
+modules here; ops/bn_act.py fuses it into the BN epilogue (act_kind 3 of
+csrc/bn_act.hip) when BDBNN_FUSE_RPRELU=1.
 """
 
 import torch
@@ -12,6 +16,7 @@ import torch.nn.functional as F
 
 from .. import _C
 from ._vec8 import tensor_vec8_supported
+from .binarize import LearnableBias
 
 
 class _ChannelPReLUFn(torch.autograd.Function):
@@ -53,3 +58,20 @@ class ChannelPReLU(nn.Module):
 
     def extra_repr(self):
         return f"num_parameters={self.num_parameters}"
+
+
+class RPReLU(nn.Module):
+    """ReActNet RPReLU: shift -> PReLU -> shift, per channel.
+
+    Parameters: move1.bias [1,C,1,1], prelu.weight [C], move2.bias
+    [1,C,1,1].  forward() is the unfused composition; fused_bn_act reads
+    the three parameters directly on its fused path."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.move1 = LearnableBias(channels)
+        self.prelu = ChannelPReLU(channels)
+        self.move2 = LearnableBias(channels)
+
+    def forward(self, x):
+        return self.move2(self.prelu(self.move1(x)))

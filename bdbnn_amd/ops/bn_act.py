@@ -12,28 +12,43 @@ CPU (and any tensor ops/_vec8.py rules out: not 4-D, C not a power of two
 in [8, 1024], dtype other than fp32 / bf16): exact composition fallback.
 """
 
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _C
 from ._vec8 import tensor_vec8_supported
-from .activations import ChannelPReLU
+from .activations import ChannelPReLU, RPReLU
 from .pool import FusedMaxPool2d
 
-_ACT_NONE, _ACT_PRELU, _ACT_RELU = 0, 1, 2
+_ACT_NONE, _ACT_PRELU, _ACT_RELU, _ACT_RPRELU = 0, 1, 2, 3
+
+# BDBNN_FUSE_RPRELU=1: an RPReLU tail (ReAct models) runs inside the BN
+# kernels as act_kind 3 instead of as three elementwise modules after them.
+# Off by default: under autocast the fused output keeps the conv output's
+# dtype (bf16), where the composition's fp32 shift parameters promote every
+# block activation to fp32 — a numerics change the user opts into
+# (docs/TUNING.md).
+_FUSE_RPRELU = os.environ.get("BDBNN_FUSE_RPRELU", "0") == "1"
 
 
 class _BNActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, skip, gamma, beta, a, running_mean, running_var,
                 momentum, eps, act_kind, training, s1=None, s2=None,
-                want_pack=False, defer_cell=None):
+                want_pack=False, defer_cell=None, b1=None, b2=None):
         nat = _C.native_required()
         res = nat.bn_act_fwd_train(
             x, skip, gamma, beta, a, running_mean, running_var,
-            momentum, eps, act_kind, s1, s2, want_pack)
+            momentum, eps, act_kind, s1, s2, want_pack, b1, b2)
         out, z, mean, invstd = res[:4]
+        # RPReLU's shifts (kind 3): backward never reads them (the saved
+        # plane z already holds u = z + b1); their grads go back in the
+        # parameters' own shape and dtype
+        ctx.shift_like = ((b1.shape, b1.dtype), (b2.shape, b2.dtype)) \
+            if act_kind == _ACT_RPRELU else None
         ctx.save_for_backward(x, z, mean, invstd, gamma,
                               a if a is not None else torch.empty(0))
         ctx.act_kind = act_kind
@@ -57,9 +72,15 @@ class _BNActFn(torch.autograd.Function):
     def backward(ctx, dy, _gxpk=None, _gmpk=None):
         x, z, mean, invstd, gamma, a = ctx.saved_tensors
         nat = _C.native_required()
-        dx, dskip, dgamma, dbeta, da = nat.bn_act_bwd(
+        res = nat.bn_act_bwd(
             dy, z, x, mean, invstd, gamma,
             a if ctx.has_a else None, ctx.act_kind, ctx.has_skip)
+        dx, dskip, dgamma, dbeta, da = res[:5]
+        db1 = db2 = None
+        if ctx.shift_like is not None:
+            (sh1, dt1), (sh2, dt2) = ctx.shift_like
+            db1 = res[5].to(dt1).view(sh1)
+            db2 = res[6].to(dt2).view(sh2)
         skip_grad = dskip if ctx.has_skip else None
         if ctx.defer_cell is not None and skip_grad is not None:
             ctx.defer_cell["g"] = skip_grad
@@ -68,7 +89,7 @@ class _BNActFn(torch.autograd.Function):
                 dgamma, dbeta,
                 da if ctx.has_a else None,
                 None, None, None, None, None, None, None, None, None,
-                None)
+                None, db1, db2)
 
 
 class _BNReluPoolFn(torch.autograd.Function):
@@ -135,7 +156,9 @@ def fused_bn_relu_maxpool(x, bn: nn.BatchNorm2d, pool, pack=False):
 
 def fused_bn_act(x, bn: nn.BatchNorm2d, act=None, skip=None, stats=None,
                  pack=False, defer_skip_cell=None):
-    """BN(x) (+skip) then act.  act: None | ChannelPReLU | 'relu'.
+    """BN(x) (+skip) then act.  act: None | ChannelPReLU | 'relu' | RPReLU
+    (fused only with BDBNN_FUSE_RPRELU=1; any other module runs unfused
+    after BN+add).
 
     stats: optional (sum, sumsq) per channel of x, pre-accumulated by the
     producing conv's epilogue — skips BN's own stats read pass.
@@ -144,8 +167,13 @@ def fused_bn_act(x, bn: nn.BatchNorm2d, act=None, skip=None, stats=None,
     bitplanes, packed in the epilogue (the conv then skips its own pack
     read pass).  Returns (out, (xp, mp) | None); only the fused training
     path with C % 32 == 0 produces a pack — callers must handle None."""
+    b1 = b2 = None
     if isinstance(act, ChannelPReLU):
         act_kind, a = _ACT_PRELU, act.weight
+    elif (_FUSE_RPRELU and isinstance(act, RPReLU)
+          and tensor_vec8_supported(x) and _C.has_native()):
+        act_kind, a = _ACT_RPRELU, act.prelu.weight
+        b1, b2 = act.move1.bias, act.move2.bias
     elif act == "relu":
         act_kind, a = _ACT_RELU, None
     elif act is None:
@@ -166,7 +194,7 @@ def fused_bn_act(x, bn: nn.BatchNorm2d, act=None, skip=None, stats=None,
         out, xpk, mpk = _BNActFn.apply(
             x, skip, bn.weight, bn.bias, a, bn.running_mean, bn.running_var,
             bn.momentum if bn.momentum is not None else 0.1, bn.eps,
-            act_kind, True, s1, s2, want_pack, defer_skip_cell)
+            act_kind, True, s1, s2, want_pack, defer_skip_cell, b1, b2)
         if pack:
             return out, ((xpk, mpk) if want_pack else None)
         return out
@@ -175,14 +203,14 @@ def fused_bn_act(x, bn: nn.BatchNorm2d, act=None, skip=None, stats=None,
         nat = _C.native_required()
         out = nat.bn_act_eval(x, skip, bn.weight, bn.bias, a,
                               bn.running_mean, bn.running_var, bn.eps,
-                              act_kind)
+                              act_kind, b1, b2)
         return (out, None) if pack else out
 
     # composition fallback (CPU / oracle)
     z = bn(x)
     if skip is not None:
         z = z + skip
-    if act_kind == _ACT_PRELU:
+    if act_kind in (_ACT_PRELU, _ACT_RPRELU):
         out = act(z)
     elif act_kind == _ACT_RELU:
         out = F.relu(z)
