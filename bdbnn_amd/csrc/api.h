@@ -63,6 +63,19 @@ void bdbnn_xnor_conv_fwd(
     int N, int H, int W, int C, int K, int KH, int KW, int stride, int pad,
     int Ho, int Wo, hipStream_t stream);
 
+// ---- xnor_conv_mfma.hip (the same conv on i8 MFMA; 3x3/p1, s1 or s2,
+// C % 64 == 0, K % 64 == 0, no BN statistics) ----
+int bdbnn_xnor_mfma_supported(int C, int K, int KH, int KW, int stride,
+                              int pad);
+// supported AND routed there by default AND BDBNN_XNOR_MFMA != 0
+int bdbnn_xnor_mfma_routed(int C, int K, int KH, int KW, int stride,
+                           int pad);
+// 0 launched, -1 unsupported shape, -2 tensor too large for int indices
+int bdbnn_xnor_conv_mfma_fwd(
+    const uint32_t* xp, const uint32_t* wp, const float* alpha, void* out,
+    bool out_bf16, int N, int H, int W, int C, int K, int KH, int KW,
+    int stride, int pad, int Ho, int Wo, hipStream_t stream);
+
 // ---- stem_conv.hip ----
 void bdbnn_stem_pack_x4(const void* x, void* x4, int64_t npix, bool bf16,
                         hipStream_t stream);

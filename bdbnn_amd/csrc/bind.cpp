@@ -5,6 +5,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <string>
 #include <unordered_map>
 #include <utility>
@@ -363,10 +364,17 @@ at::Tensor weight_decode(const at::Tensor& wp, const at::Tensor& alpha,
 
 // ---------------- xnor conv ----------------
 
-std::vector<at::Tensor> xnor_conv_fwd(
+// which kernel a forward conv call runs: by the routing table of
+// xnor_conv_mfma.hip (kAuto), or forced for tests and benchmarks
+enum XnorRoute { kAuto, kMfma, kValu };
+
+// calls since load that took {MFMA, VALU}: the routing tests read them
+static std::atomic<int64_t> g_xnor_route_calls[2];
+
+std::vector<at::Tensor> xnor_conv_route(
     const at::Tensor& xp, const at::Tensor& wp, const at::Tensor& alpha,
     const at::Tensor& stab, int64_t C, int64_t stride, int64_t pad,
-    bool out_bf16, bool want_stats) {
+    bool out_bf16, bool want_stats, XnorRoute route) {
   TORCH_CHECK(xp.is_cuda() && xp.dim() == 4 && xp.scalar_type() == at::kInt,
               "xnor_conv: packed activations int32 [N,H,W,CW]");
   TORCH_CHECK(wp.dim() == 4, "xnor_conv: packed weights [K,KH,KW,CW]");
@@ -375,6 +383,8 @@ std::vector<at::Tensor> xnor_conv_fwd(
   TORCH_CHECK(KH * KW * wp.size(3) <= 160,
               "xnor_conv: KH*KW*ceil(C/32) must be <= 160 "
               "(kernel address-table size; C <= 512 at 3x3)");
+  TORCH_CHECK(KH * KW <= 32,
+              "xnor_conv: at most 32 taps (invalid-tap bitmask width)");
   int Ho = (int)((H + 2 * pad - KH) / stride + 1);
   int Wo = (int)((W + 2 * pad - KW) / stride + 1);
   auto out = at::empty({N, K, Ho, Wo},
@@ -390,14 +400,73 @@ std::vector<at::Tensor> xnor_conv_fwd(
     s1p = s1.data_ptr<float>();
     s2p = s2.data_ptr<float>();
   }
+  bool mfma = route == kMfma;
+  if (route == kAuto)
+    mfma = !want_stats && bdbnn_xnor_mfma_routed((int)C, K, KH, KW,
+                                                 (int)stride, (int)pad);
+  if (mfma) {
+    TORCH_CHECK(!want_stats, "xnor_conv_mfma: no BN statistics epilogue");
+    TORCH_CHECK(wp.size(3) * 32 == C && xp.size(3) == wp.size(3),
+                "xnor_conv_mfma: C must equal 32 * CW of both operands");
+    int rc = bdbnn_xnor_conv_mfma_fwd(
+        (const uint32_t*)xp.data_ptr<int>(),
+        (const uint32_t*)wp.data_ptr<int>(), alpha.data_ptr<float>(),
+        out.data_ptr(), out_bf16, N, H, W, (int)C, K, KH, KW, (int)stride,
+        (int)pad, Ho, Wo, cur_stream());
+    TORCH_CHECK(rc == 0, "xnor_conv_mfma: ",
+                rc == -1 ? "unsupported shape" : "tensor too large");
+    ++g_xnor_route_calls[0];
+    return {out};
+  }
   bdbnn_xnor_conv_fwd((const uint32_t*)xp.data_ptr<int>(),
                       (const uint32_t*)wp.data_ptr<int>(),
                       alpha.data_ptr<float>(), stab.data_ptr<float>(),
                       out.data_ptr(), s1p, s2p, out_bf16, N, H, W, (int)C,
                       K, KH, KW, (int)stride, (int)pad, Ho, Wo,
                       cur_stream());
+  ++g_xnor_route_calls[1];
   if (want_stats) return {out, s1, s2};
   return {out};
+}
+
+std::vector<at::Tensor> xnor_conv_fwd(
+    const at::Tensor& xp, const at::Tensor& wp, const at::Tensor& alpha,
+    const at::Tensor& stab, int64_t C, int64_t stride, int64_t pad,
+    bool out_bf16, bool want_stats) {
+  return xnor_conv_route(xp, wp, alpha, stab, C, stride, pad, out_bf16,
+                         want_stats, kAuto);
+}
+
+// the two kernels by name, whatever the routing table says
+at::Tensor xnor_conv_mfma_fwd(const at::Tensor& xp, const at::Tensor& wp,
+                              const at::Tensor& alpha, int64_t C,
+                              int64_t stride, int64_t pad, bool out_bf16) {
+  TORCH_CHECK(wp.dim() == 4 &&
+                  bdbnn_xnor_mfma_supported((int)C, (int)wp.size(0),
+                                            (int)wp.size(1), (int)wp.size(2),
+                                            (int)stride, (int)pad),
+              "xnor_conv_mfma_fwd: shape not supported by the MFMA kernel");
+  return xnor_conv_route(xp, wp, alpha, alpha, C, stride, pad, out_bf16,
+                         false, kMfma)[0];
+}
+
+std::vector<at::Tensor> xnor_conv_valu_fwd(
+    const at::Tensor& xp, const at::Tensor& wp, const at::Tensor& alpha,
+    const at::Tensor& stab, int64_t C, int64_t stride, int64_t pad,
+    bool out_bf16, bool want_stats) {
+  return xnor_conv_route(xp, wp, alpha, stab, C, stride, pad, out_bf16,
+                         want_stats, kValu);
+}
+
+bool xnor_mfma_supported(int64_t C, int64_t K, int64_t KH, int64_t KW,
+                         int64_t stride, int64_t pad) {
+  return bdbnn_xnor_mfma_supported((int)C, (int)K, (int)KH, (int)KW,
+                                   (int)stride, (int)pad) != 0;
+}
+
+// (calls on the MFMA kernel, calls on the VALU kernel) since load
+std::vector<int64_t> xnor_route_calls() {
+  return {g_xnor_route_calls[0].load(), g_xnor_route_calls[1].load()};
 }
 
 
@@ -1353,7 +1422,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_packed", &decode_packed, "packed signs -> +-1 NHWC tensor");
   m.def("mask_mul_packed", &mask_mul_packed, "dx = mask_bit ? g : 0");
   m.def("weight_decode", &weight_decode, "packed weights -> alpha*(+-1)");
-  m.def("xnor_conv_fwd", &xnor_conv_fwd, "bit-packed XNOR+popcount conv");
+  m.def("xnor_conv_fwd", &xnor_conv_fwd,
+        "binary conv forward (i8 MFMA or XNOR+popcount, by the routing "
+        "table)");
+  m.def("xnor_mfma_supported", &xnor_mfma_supported,
+        "(C, K, KH, KW, stride, pad): can the i8 MFMA forward run it");
+  m.def("xnor_conv_mfma_fwd", &xnor_conv_mfma_fwd,
+        "binary conv forward, i8 MFMA kernel forced");
+  m.def("xnor_conv_valu_fwd", &xnor_conv_valu_fwd,
+        "binary conv forward, XNOR+popcount kernel forced");
+  m.def("xnor_route_calls", &xnor_route_calls,
+        "(MFMA, VALU) forward conv calls since load");
   m.def("stem_conv_fwd", &stem_conv_fwd,
         "MFMA 7x7/2 stem conv fwd (returns out, packed x4)");
   m.def("stem_conv_wrw", &stem_conv_wrw, "MFMA stem conv weight grad");

@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void xnor_conv_kernel(
   __shared__ uint32_t a_lds[2][CHUNK][TM];
   __shared__ uint32_t w_lds[2][CHUNK][TILE_K];
   __shared__ int row_basecw[TM];      // pixel index of tap (0,0), x CW
-  __shared__ unsigned short row_inv[TM];      // invalid-tap bitmask (T<=9)
+  __shared__ uint32_t row_inv[TM];    // invalid-tap bitmask (T <= 32)
   __shared__ int off_tab[MAX_WORDS];          // (kh*W+kw)*CW + cw per word
   __shared__ unsigned char tap_tab[MAX_WORDS];
   __shared__ float csum[2][TILE_K];           // per-channel stats partials
@@ -78,14 +78,14 @@ __global__ __launch_bounds__(256) void xnor_conv_kernel(
   // ---- per-block metadata ----
   for (int r = tid; r < TM; r += blockDim.x) {
     int64_t sp = m0 + r;
-    if (sp >= M) { row_basecw[r] = 0; row_inv[r] = 0xffff; continue; }
+    if (sp >= M) { row_basecw[r] = 0; row_inv[r] = 0xffffffffu; continue; }
     int n = int(sp / ((int64_t)p.Ho * p.Wo));
     int rem = int(sp % ((int64_t)p.Ho * p.Wo));
     int oy = rem / p.Wo, ox = rem % p.Wo;
     int iy0 = oy * p.stride - p.pad;
     int ix0 = ox * p.stride - p.pad;
     row_basecw[r] = ((n * p.H + iy0) * p.W + ix0) * p.CW;
-    unsigned short inv = 0;
+    uint32_t inv = 0;
     for (int t = 0; t < p.T; ++t) {
       int kh = t / p.KW, kw = t % p.KW;
       int iy = iy0 + kh, ix = ix0 + kw;

@@ -30,6 +30,7 @@ sources = [os.path.join(CSRC, f) for f in (
     "conv_bwd_s2.hip",
     "stem_conv.hip",
     "xnor_conv.hip",
+    "xnor_conv_mfma.hip",
     "kurtosis.hip",
     "kd.hip",
     "optim.hip",
