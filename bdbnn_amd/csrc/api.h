@@ -75,6 +75,17 @@ int bdbnn_xnor_conv_mfma_fwd(
     const uint32_t* xp, const uint32_t* wp, const float* alpha, void* out,
     bool out_bf16, int N, int H, int W, int C, int K, int KH, int KW,
     int stride, int pad, int Ho, int Wo, hipStream_t stream);
+// The same conv with the eval-mode block tail in its epilogue (inference):
+// out = act(sc_k * round(alpha_k * dot) + sh_k (+ skip)), act_kind as
+// bn_act.hip's, (sc, sh) from bdbnn_bn_fold; a for kinds 1 and 3, b2 for
+// kind 3, skip (out's dtype and layout) and plane ([N,Ho,Wo,K/32] sign
+// plane of out) may be null.  Return codes as above, -3 bad act operands.
+int bdbnn_xnor_conv_bn_act_fwd(
+    const uint32_t* xp, const uint32_t* wp, const float* alpha,
+    const float* sc, const float* sh, const float* a, const float* b2,
+    const void* skip, void* out, uint32_t* plane, int act_kind,
+    bool out_bf16, int N, int H, int W, int C, int K, int KH, int KW,
+    int stride, int pad, int Ho, int Wo, hipStream_t stream);
 
 // ---- stem_conv.hip ----
 void bdbnn_stem_pack_x4(const void* x, void* x4, int64_t npix, bool bf16,
@@ -151,6 +162,11 @@ void bdbnn_bn_act_eval(const void* x, const void* skip, const float* rm,
                        const float* b2, void* out, int64_t n, int C,
                        int act_kind, float eps, bool bf16,
                        hipStream_t stream);
+// the eval kernel's folded constants on their own: sc = gamma * rsqrt(rv +
+// eps), sh = beta - rm * sc (+ b1 when not null), fp32 [C]
+void bdbnn_bn_fold(const float* gamma, const float* beta, const float* rm,
+                   const float* rv, const float* b1, float* sc, float* sh,
+                   int C, float eps, hipStream_t stream);
 
 // ---- bn_pool.hip ----
 void bdbnn_bn_relu_maxpool_fwd(

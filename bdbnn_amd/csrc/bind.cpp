@@ -469,6 +469,113 @@ std::vector<int64_t> xnor_route_calls() {
   return {g_xnor_route_calls[0].load(), g_xnor_route_calls[1].load()};
 }
 
+// ---- inference: conv + folded eval BN (+ skip) + act (+ sign plane) ----
+
+// launches of the fused inference conv since load (the engine tests read it)
+static std::atomic<int64_t> g_xnor_fused_calls;
+
+int64_t xnor_fused_calls() { return g_xnor_fused_calls.load(); }
+
+// (sc, sh) of an eval-mode BN as bn_act_eval_kernel computes them for
+// itself, by the same device function; b1 (RPReLU) is added to sh
+std::vector<at::Tensor> bn_fold(const at::Tensor& gamma,
+                                const at::Tensor& beta, const at::Tensor& rm,
+                                const at::Tensor& rv, double eps,
+                                const c10::optional<at::Tensor>& b1) {
+  TORCH_CHECK(gamma.is_cuda() && gamma.numel() > 0,
+              "bn_fold: gamma must be a non-empty CUDA tensor");
+  int64_t C = gamma.numel();
+  TORCH_CHECK(beta.numel() == C && rm.numel() == C && rv.numel() == C &&
+                  (!b1.has_value() || b1->numel() == C),
+              "bn_fold: per-channel tensors must have C elements");
+  auto gf = chan_f32(gamma);
+  auto bf = chan_f32(beta);
+  auto rmf = chan_f32(rm);
+  auto rvf = chan_f32(rv);
+  at::Tensor b1f;
+  const float* b1_ptr = opt_chan_ptr(b1, b1f);
+  auto sc = at::empty({C}, gf.options());
+  auto sh = at::empty({C}, gf.options());
+  bdbnn_bn_fold(gf.data_ptr<float>(), bf.data_ptr<float>(),
+                rmf.data_ptr<float>(), rvf.data_ptr<float>(), b1_ptr,
+                sc.data_ptr<float>(), sh.data_ptr<float>(), (int)C,
+                (float)eps, cur_stream());
+  return {sc, sh};
+}
+
+py::list xnor_conv_bn_act_fwd(
+    const at::Tensor& xp, const at::Tensor& wp, const at::Tensor& alpha,
+    const at::Tensor& sc, const at::Tensor& sh,
+    const c10::optional<at::Tensor>& a, const c10::optional<at::Tensor>& b2,
+    const c10::optional<at::Tensor>& skip, int64_t C, int64_t stride,
+    int64_t pad, int64_t act_kind, bool out_bf16, bool want_pack) {
+  const char* who = "xnor_conv_bn_act_fwd: ";
+  TORCH_CHECK(xp.is_cuda() && xp.dim() == 4 && xp.scalar_type() == at::kInt &&
+                  xp.is_contiguous(),
+              who, "packed activations int32 [N,H,W,CW]");
+  TORCH_CHECK(wp.is_cuda() && wp.dim() == 4 && wp.scalar_type() == at::kInt &&
+                  wp.is_contiguous(),
+              who, "packed weights int32 [K,KH,KW,CW]");
+  int N = (int)xp.size(0), H = (int)xp.size(1), W = (int)xp.size(2);
+  int K = (int)wp.size(0), KH = (int)wp.size(1), KW = (int)wp.size(2);
+  TORCH_CHECK(bdbnn_xnor_mfma_supported((int)C, K, KH, KW, (int)stride,
+                                        (int)pad),
+              who, "shape not supported by the MFMA kernel");
+  TORCH_CHECK(wp.size(3) * 32 == C && xp.size(3) == wp.size(3),
+              who, "C must equal 32 * CW of both operands");
+  TORCH_CHECK(act_kind >= 0 && act_kind <= 3, who, "act_kind must be 0..3");
+  // the kernel reads the per-channel operands as float4 through float*
+  auto chan_ok = [&](const at::Tensor& t) {
+    return is_f32_chan(t, K) && (uintptr_t)t.data_ptr() % 16 == 0;
+  };
+  TORCH_CHECK(chan_ok(alpha) && chan_ok(sc) && chan_ok(sh),
+              who, "alpha, sc, sh must be contiguous fp32 CUDA [K]");
+  const bool need_a = act_kind == 1 || act_kind == 3;
+  TORCH_CHECK(!need_a || a.has_value(), who, "PReLU needs its slopes a");
+  TORCH_CHECK(act_kind != 3 || b2.has_value(), who, "RPReLU needs b2");
+  TORCH_CHECK((!need_a || chan_ok(*a)) && (act_kind != 3 || chan_ok(*b2)),
+              who, "a, b2 must be contiguous fp32 CUDA [K]");
+  int Ho = (int)((H + 2 * pad - KH) / stride + 1);
+  int Wo = (int)((W + 2 * pad - KW) / stride + 1);
+  auto out = at::empty({N, K, Ho, Wo},
+                       xp.options().dtype(out_bf16 ? at::kBFloat16
+                                                   : at::kFloat),
+                       at::MemoryFormat::ChannelsLast);
+  const void* skip_ptr = nullptr;
+  if (skip.has_value()) {
+    TORCH_CHECK(skip->is_cuda() && skip->sizes() == out.sizes() &&
+                    skip->scalar_type() == out.scalar_type() &&
+                    skip->is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                    (uintptr_t)skip->data_ptr() % 16 == 0,
+                who, "skip must have out's shape, dtype and channels_last "
+                     "layout");
+    skip_ptr = skip->data_ptr();
+  }
+  at::Tensor plane;
+  uint32_t* plane_ptr = nullptr;
+  if (want_pack) {
+    plane = at::empty({N, Ho, Wo, K / 32}, xp.options());
+    plane_ptr = (uint32_t*)plane.data_ptr<int>();
+  }
+  int rc = bdbnn_xnor_conv_bn_act_fwd(
+      (const uint32_t*)xp.data_ptr<int>(),
+      (const uint32_t*)wp.data_ptr<int>(), alpha.data_ptr<float>(),
+      sc.data_ptr<float>(), sh.data_ptr<float>(),
+      need_a ? a->data_ptr<float>() : nullptr,
+      act_kind == 3 ? b2->data_ptr<float>() : nullptr, skip_ptr,
+      out.data_ptr(), plane_ptr, (int)act_kind, out_bf16, N, H, W, (int)C, K,
+      KH, KW, (int)stride, (int)pad, Ho, Wo, cur_stream());
+  TORCH_CHECK(rc == 0, who,
+              rc == -1 ? "unsupported shape"
+                       : rc == -2 ? "tensor too large" : "bad act operands");
+  ++g_xnor_fused_calls;
+  py::list res;
+  res.append(out);
+  if (want_pack) res.append(plane);
+  else res.append(py::none());
+  return res;
+}
+
 
 // ---------------- stem conv (7x7/2, C=3 -> 64) ----------------
 
@@ -1433,6 +1540,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "binary conv forward, XNOR+popcount kernel forced");
   m.def("xnor_route_calls", &xnor_route_calls,
         "(MFMA, VALU) forward conv calls since load");
+  m.def("bn_fold", &bn_fold,
+        "eval BN folded as bn_act_eval does it -> (sc, sh) fp32 [C]; b1 "
+        "(RPReLU) is added to sh",
+        py::arg("gamma"), py::arg("beta"), py::arg("rm"), py::arg("rv"),
+        py::arg("eps"), py::arg("b1") = py::none());
+  m.def("xnor_conv_bn_act_fwd", &xnor_conv_bn_act_fwd,
+        "inference: i8 MFMA binary conv + folded BN (+ skip) + act in one "
+        "kernel -> [out, sign plane of out | None]",
+        py::arg("xp"), py::arg("wp"), py::arg("alpha"), py::arg("sc"),
+        py::arg("sh"), py::arg("a"), py::arg("b2"), py::arg("skip"),
+        py::arg("C"), py::arg("stride"), py::arg("pad"), py::arg("act_kind"),
+        py::arg("out_bf16"), py::arg("want_pack"));
+  m.def("xnor_fused_calls", &xnor_fused_calls,
+        "launches of xnor_conv_bn_act_fwd since load");
   m.def("stem_conv_fwd", &stem_conv_fwd,
         "MFMA 7x7/2 stem conv fwd (returns out, packed x4)");
   m.def("stem_conv_wrw", &stem_conv_wrw, "MFMA stem conv weight grad");

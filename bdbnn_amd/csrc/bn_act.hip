@@ -329,9 +329,8 @@ __global__ void bn_act_eval_kernel(const T* __restrict__ x,
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     int cc = m.c0 + j;
-    float is = rsqrtf(rv[cc] + eps);
-    sc[j] = gamma[cc] * is;
-    sh[j] = beta[cc] - rm[cc] * sc[j];
+    bn_eval_scale_shift(gamma[cc], beta[cc], rm[cc], rv[cc], eps, sc[j],
+                        sh[j]);
     av[j] = (ACT == 1 || ACT == 3) ? a[cc] : 0.f;
     if (ACT == 3) sh[j] += b1[cc];   // as in bn_act_fwd_kernel
     b2v[j] = (ACT == 3) ? b2[cc] : 0.f;
@@ -342,16 +341,31 @@ __global__ void bn_act_eval_kernel(const T* __restrict__ x,
     load8(x, i, v);
     if (skip != nullptr) load8(skip, i, s);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float zv = sc[j] * v[j] + sh[j];
-      if (skip != nullptr) zv += s[j];
-      o[j] = zv;
-      if (ACT == 1) o[j] = zv > 0.f ? zv : av[j] * zv;
-      else if (ACT == 2) o[j] = fmaxf(zv, 0.f);
-      else if (ACT == 3) o[j] = (zv > 0.f ? zv : av[j] * zv) + b2v[j];
-    }
+    for (int j = 0; j < 8; ++j)
+      o[j] = bn_eval_act<ACT>(sc[j], v[j], sh[j], skip != nullptr, s[j],
+                              av[j], b2v[j]);
     store8(out, i, o);
   }
+}
+
+// the eval kernel's folded (sc, sh) on their own, computed on the device by
+// the same function: what the inference engine folds once per BN and hands
+// to the fused conv epilogue (xnor_conv_mfma.hip) equals, bit for bit, what
+// bn_act_eval_kernel computes for itself on every launch
+__global__ void bn_fold_kernel(const float* __restrict__ gamma,
+                               const float* __restrict__ beta,
+                               const float* __restrict__ rm,
+                               const float* __restrict__ rv,
+                               const float* __restrict__ b1,
+                               float* __restrict__ sc, float* __restrict__ sh,
+                               int C, float eps) {
+  int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  float s, h;
+  bn_eval_scale_shift(gamma[c], beta[c], rm[c], rv[c], eps, s, h);
+  if (b1 != nullptr) h += b1[c];   // RPReLU
+  sc[c] = s;
+  sh[c] = h;
 }
 
 // ---------------- launchers ----------------
@@ -473,4 +487,12 @@ extern "C" void bdbnn_bn_act_eval(const void* x, const void* skip,
           (T*)out, n_pix, C, eps);
     });
   });
+}
+
+extern "C" void bdbnn_bn_fold(const float* gamma, const float* beta,
+                              const float* rm, const float* rv,
+                              const float* b1, float* sc, float* sh, int C,
+                              float eps, hipStream_t stream) {
+  bn_fold_kernel<<<(C + 255) / 256, 256, 0, stream>>>(gamma, beta, rm, rv, b1,
+                                                      sc, sh, C, eps);
 }

@@ -28,7 +28,19 @@
 //
 // Covers 3x3 / pad 1 / stride 1 or 2 with C % 64 == 0 and K % 64 == 0
 // (every 3x3 conv of ResNet-18/34); everything else stays on xnor_conv.hip.
+//
+// Inference epilogue (EPI >= 0, bdbnn_xnor_conv_bn_act_fwd): the block tail
+// that follows the conv in eval mode runs on the accumulator registers
+// instead of as bn_act_eval_kernel (+ sign_pack_nhwc for the next conv):
+//   v   = round_storage<TO>(alpha_k * float(acc))   // the plain store
+//   out = act(sc_k * v + sh_k (+ skip))             // bn_eval_act<EPI>
+// with (sc, sh) folded once by bn_fold_kernel (bn_act.hip).  Both functions
+// are bn_act_eval_kernel's own (bn_affine.h), so `out` is bit for bit the
+// composition's.  Optionally the sign plane of `out` as stored is written
+// for the consuming conv (act_masks.h convention; no clip-mask plane).
 #include "conv_bwd_common.h"
+#include "bn_affine.h"
+#include "act_masks.h"
 #include <cstdlib>
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
@@ -43,6 +55,16 @@ struct XnorMfmaParams {
   int segs;              // 64-column segments per output row (1 if Wo <= 64)
   int bands_per_image;   // ceil(Ho / RB)
   int total_slots;       // N * bands_per_image * segs
+};
+
+// Operands of the inference epilogue; unused (all null) when EPI < 0.
+struct XnorEpiArgs {
+  const float* sc;       // [K] folded BN scale
+  const float* sh;       // [K] folded BN shift (+ b1 for kind 3)
+  const float* a;        // [K] PReLU slopes (kinds 1, 3)
+  const float* b2;       // [K] RPReLU output shift (kind 3)
+  const void* skip;      // TO [N,Ho,Wo,K] residual, or null
+  uint32_t* plane;       // [N,Ho,Wo,K/32] sign plane of out, or null
 };
 
 // 4 bits -> 4 bytes holding the bit (0/1): the four shifted copies of the
@@ -70,12 +92,13 @@ __device__ __forceinline__ int xm_slot(int row, int q) {
   return row * XM_BK + ((q ^ ((row >> 1) & 3)) << 4);
 }
 
-// S: stride;  WP/RB/GB: padded-width class (see above)
-template <typename TO, int S, int WP, int RB, int GB>
+// S: stride;  WP/RB/GB: padded-width class (see above);  EPI: -1 stores
+// alpha * dot, 0..3 the inference epilogue with that act_kind (bn_act.hip)
+template <typename TO, int S, int WP, int RB, int GB, int EPI = -1>
 __global__ __launch_bounds__(512, 2) void xnor_conv_mfma_kernel(
     const uint32_t* __restrict__ xp, const uint32_t* __restrict__ wp,
     const float* __restrict__ alpha, TO* __restrict__ out, XnorMfmaParams p,
-    int grid_m) {
+    int grid_m, XnorEpiArgs e) {
   constexpr int HR = (RB - 1) * S + 3;        // halo rows per band
   constexpr int WH = (WP - 1) * S + 3;        // halo row width
   constexpr int NHE = GB * HR * WH;           // halo entries (64 B each)
@@ -95,6 +118,9 @@ __global__ __launch_bounds__(512, 2) void xnor_conv_mfma_kernel(
   __shared__ int he_base[NHE];      // input pixel index of halo entry, or -1
   __shared__ int tab_he[XM_BM];     // halo entry of tap (0,0) of pixel m
   __shared__ int tab_out[XM_BM];    // output pixel index, or -1
+  // inference epilogue: the block's 64 channels of alpha, sc, sh, a, b2
+  constexpr int NOPS = EPI >= 0 ? 5 : 1;
+  __shared__ __align__(16) float eops[NOPS][XM_BN];
 
   // ---- per-block tables ----
   const int slot0 = tile * GB;
@@ -130,6 +156,16 @@ __global__ __launch_bounds__(512, 2) void xnor_conv_mfma_kernel(
       if (oy < p.Ho && ox < p.Wo) o = (n * p.Ho + oy) * p.Wo + ox;
     }
     tab_out[m] = o;
+  }
+  if constexpr (EPI >= 0) {
+    // staged once per block, read back per 4-channel group in the epilogue:
+    // an LDS read there instead of a global round trip per group
+    for (int i = tid; i < 5 * XM_BN; i += 512) {
+      const int which = i / XM_BN, kb = i - which * XM_BN;
+      const float* src = which == 0 ? alpha : which == 1 ? e.sc
+                       : which == 2 ? e.sh : which == 3 ? e.a : e.b2;
+      eops[which][kb] = src != nullptr ? src[k0 + kb] : 0.f;
+    }
   }
   __syncthreads();
 
@@ -239,6 +275,103 @@ __global__ __launch_bounds__(512, 2) void xnor_conv_mfma_kernel(
 
   // ---- epilogue: D[row = channel][col = pixel]; registers 4g..4g+3 of a
   // lane are channels 8g + 4*lh + 0..3 of its pixel (mfma32_cd_row) ----
+  if constexpr (EPI >= 0) {
+    // Per 4-channel group g the five per-channel operands come from LDS as
+    // float4 (20 live VGPRs, not 80) and serve both pixels of the lane.
+    // The skip is read at the address the output is stored to: all 8
+    // loads of a lane are issued before the first use, so a block waits
+    // for memory once, not once per group.  A lane sets the sign bits of
+    // its 16 channels in place (bit = channel within the wave's 32); lanes
+    // l and l + 32 hold the two halves of one plane word and combine them
+    // with one exchange.
+    using SkipVec = std::conditional_t<sizeof(TO) == 2, uint2, float4>;
+    const TO* __restrict__ skip = (const TO*)e.skip;
+    const int pix[2] = {tab_out[wm0 + lrow], tab_out[wm0 + 32 + lrow]};
+    // element offset of the lane's channel 0 of each pixel, in out and in
+    // skip; a lane without a pixel computes on pixel 0's row (in bounds),
+    // stores nothing, and its sign bits are dropped below
+    const int64_t row[2] = {
+        (int64_t)(pix[0] < 0 ? 0 : pix[0]) * p.K + k0 + wc,
+        (int64_t)(pix[1] < 0 ? 0 : pix[1]) * p.K + k0 + wc};
+    // Without a skip every element adds -0.0f, the one addend that leaves
+    // each float as it is (+0 + -0 = +0, -0 + -0 = -0): bit for bit the
+    // eval kernel's "no add", without a select per element.
+    SkipVec sk[4][2];
+    if (skip != nullptr) {   // uniform; no branch per load, so one wait
+#pragma unroll
+      for (int half = 0; half < 2; ++half)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          sk[g][half] = *(const SkipVec*)&skip[
+              row[half] + mfma32_cd_row(4 * g, lh)];
+    } else {
+#pragma unroll
+      for (int half = 0; half < 2; ++half)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          if constexpr (sizeof(TO) == 2)
+            sk[g][half] = uint2{0x80008000u, 0x80008000u};
+          else
+            sk[g][half] = float4{-0.f, -0.f, -0.f, -0.f};
+        }
+    }
+    uint32_t bits[2] = {0u, 0u};
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int ch = mfma32_cd_row(4 * g, lh);
+      float al[4], sc[4], sh[4], av[4] = {0.f, 0.f, 0.f, 0.f},
+            b2v[4] = {0.f, 0.f, 0.f, 0.f};
+      *(float4*)al = *(const float4*)&eops[0][wc + ch];
+      *(float4*)sc = *(const float4*)&eops[1][wc + ch];
+      *(float4*)sh = *(const float4*)&eops[2][wc + ch];
+      if constexpr (EPI == 1 || EPI == 3)
+        *(float4*)av = *(const float4*)&eops[3][wc + ch];
+      if constexpr (EPI == 3) *(float4*)b2v = *(const float4*)&eops[4][wc + ch];
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const i32x16& acc = half ? acc1 : acc0;
+        float s[4], r[4];
+        if constexpr (sizeof(TO) == 2) {
+          const uint16_t* u = (const uint16_t*)&sk[g][half];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) s[j] = bf16_to_f32(u[j]);
+        } else {
+          *(float4*)s = sk[g][half];
+        }
+        uint16_t vals[4];   // bf16 only: rounded once, stored and re-read
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float v = round_storage<TO>(al[j] * float(acc[4 * g + j]));
+          r[j] = bn_eval_act<EPI>(sc[j], v, sh[j], true, s[j], av[j],
+                                  b2v[j]);
+          if constexpr (sizeof(TO) == 2) {
+            vals[j] = f32_to_bf16(r[j]);
+            r[j] = bf16_to_f32(vals[j]);      // = round_storage<TO>(out)
+          }
+          // constant shift here, the lane half's 4 * lh once at the end
+          bits[half] |= uint32_t(sign_bit(r[j])) << (8 * g + j);
+        }
+        if (pix[half] >= 0) {
+          if constexpr (sizeof(TO) == 2)
+            *(uint2*)&out[row[half] + ch] = *(uint2*)vals;
+          else
+            *(float4*)&out[row[half] + ch] = *(float4*)r;
+        }
+      }
+    }
+    if (e.plane != nullptr) {       // uniform; every lane of the wave shuffles
+      const int64_t KW32 = p.K >> 5;
+      const int word = (k0 + wc) >> 5;
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const uint32_t mine = bits[half] << (4 * lh);
+        const uint32_t other = __shfl_xor(mine, 32);
+        if (lh == 0 && pix[half] >= 0)
+          e.plane[(int64_t)pix[half] * KW32 + word] = mine | other;
+      }
+    }
+    return;
+  }
   float al[16];
 #pragma unroll
   for (int g = 0; g < 4; ++g)
@@ -315,10 +448,12 @@ extern "C" int bdbnn_xnor_mfma_routed(int C, int K, int KH, int KW,
                                [](bool on) { return on ? 1 : 0; }) == 1;
 }
 
-extern "C" int bdbnn_xnor_conv_mfma_fwd(
+// geometry + launch of either epilogue: EPI -1 (plain) or an act_kind
+template <int EPI>
+static int xnor_mfma_launch(
     const uint32_t* xp, const uint32_t* wp, const float* alpha, void* out,
     bool out_bf16, int N, int H, int W, int C, int K, int KH, int KW,
-    int stride, int pad, int Ho, int Wo, hipStream_t stream) {
+    int stride, int pad, int Ho, int Wo, XnorEpiArgs e, hipStream_t stream) {
   if (!bdbnn_xnor_mfma_supported(C, K, KH, KW, stride, pad)) return -1;
   if ((int64_t)N * H * W > INT32_MAX || (int64_t)N * Ho * Wo > INT32_MAX)
     return -2;   // pixel indices are int
@@ -338,12 +473,45 @@ extern "C" int bdbnn_xnor_conv_mfma_fwd(
     with_dtype(out_bf16, [&](auto t) {
       using TO = decltype(t);
       if (stride == 1)
-        xnor_conv_mfma_kernel<TO, 1, G::WP, G::RB, G::GB>
-            <<<grid, 512, 0, stream>>>(xp, wp, alpha, (TO*)out, p, grid_m);
+        xnor_conv_mfma_kernel<TO, 1, G::WP, G::RB, G::GB, EPI>
+            <<<grid, 512, 0, stream>>>(xp, wp, alpha, (TO*)out, p, grid_m,
+                                       e);
       else
-        xnor_conv_mfma_kernel<TO, 2, G::WP, G::RB, G::GB>
-            <<<grid, 512, 0, stream>>>(xp, wp, alpha, (TO*)out, p, grid_m);
+        xnor_conv_mfma_kernel<TO, 2, G::WP, G::RB, G::GB, EPI>
+            <<<grid, 512, 0, stream>>>(xp, wp, alpha, (TO*)out, p, grid_m,
+                                       e);
     });
     return 0;
   });
+}
+
+extern "C" int bdbnn_xnor_conv_mfma_fwd(
+    const uint32_t* xp, const uint32_t* wp, const float* alpha, void* out,
+    bool out_bf16, int N, int H, int W, int C, int K, int KH, int KW,
+    int stride, int pad, int Ho, int Wo, hipStream_t stream) {
+  return xnor_mfma_launch<-1>(xp, wp, alpha, out, out_bf16, N, H, W, C, K,
+                              KH, KW, stride, pad, Ho, Wo, XnorEpiArgs{},
+                              stream);
+}
+
+// conv + folded eval BN (+ skip) + act (+ sign plane of out) in one launch.
+// -3: act_kind outside 0..3 or a per-channel operand it needs is null.
+extern "C" int bdbnn_xnor_conv_bn_act_fwd(
+    const uint32_t* xp, const uint32_t* wp, const float* alpha,
+    const float* sc, const float* sh, const float* a, const float* b2,
+    const void* skip, void* out, uint32_t* plane, int act_kind,
+    bool out_bf16, int N, int H, int W, int C, int K, int KH, int KW,
+    int stride, int pad, int Ho, int Wo, hipStream_t stream) {
+  if (act_kind < 0 || act_kind > 3 || sc == nullptr || sh == nullptr)
+    return -3;
+  if ((act_kind == 1 || act_kind == 3) && a == nullptr) return -3;
+  if (act_kind == 3 && b2 == nullptr) return -3;
+  XnorEpiArgs e{sc, sh, a, b2, skip, plane};
+  int rc = -3;
+  with_int<1, 2, 3, 0>(act_kind, [&](auto act) {
+    rc = xnor_mfma_launch<decltype(act)::value>(
+        xp, wp, alpha, out, out_bf16, N, H, W, C, K, KH, KW, stride, pad, Ho,
+        Wo, e, stream);
+  });
+  return rc;
 }
