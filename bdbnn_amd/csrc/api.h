@@ -203,6 +203,14 @@ void bdbnn_repack_cplane(const uint32_t* xp, uint64_t* xcp, int NH, int W,
 void bdbnn_wgrad_finish(const float* dwT, const float* w, float* dw, int C,
                         int K, int T, int nslab, hipStream_t stream);
 
+// ---- conv_wgrad3.hip (3x3/s1/p1 wgrad from the NHWC sign plane xp
+// [N][H][W][C/32]; slab contract and m-split of conv_wgrad2) ----
+// shape can run AND its class is routed here by default
+int bdbnn_wgrad3_supported(int H, int W, int C, int K);
+int bdbnn_wgrad3_nslab(int N, int H, int W, int C, int K);
+int bdbnn_conv_wgrad3(const void* g, const uint32_t* xp, float* dwT, int N,
+                      int H, int W, int C, int K, hipStream_t stream);
+
 // ---- conv_bwd_s2.hip (3x3/s2/p1 and 1x1/s2/p0 MFMA backward) ----
 int bdbnn_s2_kernels_can_run(int H, int W, int C, int K, int ks);
 int bdbnn_dgrad2_s2_supported(int H, int W, int C, int K, int ks);

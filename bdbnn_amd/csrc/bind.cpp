@@ -1298,6 +1298,32 @@ at::Tensor conv_wgrad2(const at::Tensor& g, const at::Tensor& xcp,
   return dwT;
 }
 
+// the same weight gradient straight from the NHWC sign plane xp
+// [N][H][W][C/32] (csrc/conv_wgrad3.hip); slabs as conv_wgrad2's
+at::Tensor conv_wgrad3(const at::Tensor& g, const at::Tensor& xp,
+                       int64_t C) {
+  check_grad_bf16_cl(g, "conv_wgrad3");
+  int N = (int)g.size(0), K = (int)g.size(1);
+  int H = (int)g.size(2), W = (int)g.size(3);
+  TORCH_CHECK(C >= 64 && C % 64 == 0 && K % 64 == 0 && W <= 64,
+              "conv_wgrad3: unsupported shape");
+  TORCH_CHECK(xp.is_cuda() && xp.dim() == 4 &&
+                  xp.scalar_type() == at::kInt && xp.is_contiguous() &&
+                  xp.size(0) == N && xp.size(1) == H && xp.size(2) == W &&
+                  xp.size(3) == C / 32,
+              "conv_wgrad3: xp must be contiguous int32 [N][H][W][C/32]");
+  int nslab = bdbnn_wgrad3_nslab(N, H, W, (int)C, K);
+  TORCH_CHECK(nslab > 0, "conv_wgrad3: unsupported shape");
+  // per-m-split-block partial slabs; every word is written (no memset)
+  auto dwT = at::empty({nslab, 9, C, K}, g.options().dtype(at::kFloat));
+  int rc = bdbnn_conv_wgrad3(g.data_ptr(),
+                             (const uint32_t*)xp.data_ptr<int>(),
+                             dwT.data_ptr<float>(), N, H, W, (int)C, K,
+                             cur_stream());
+  TORCH_CHECK(rc == 0, "conv_wgrad3: launch rejected the shape");
+  return dwT;
+}
+
 // ---------------- stride 2 (3x3/s2/p1, 1x1/s2/p0) ----------------
 
 // shape predicates of the stride-2 path; H, W are the INPUT (dx) size,
@@ -1615,6 +1641,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_wgrad2", &conv_wgrad2,
         "MFMA bf16 wgrad v2: all-9-tap block GEMM from sign BITS "
         "(3x3/s1/p1) -> fp32 [9][C][K]");
+  m.def("conv_wgrad3", &conv_wgrad3,
+        "MFMA bf16 wgrad v3: pipelined all-9-tap block GEMM from the NHWC "
+        "sign plane, transposed LDS reads (3x3/s1/p1) -> fp32 "
+        "[nslab][9][C][K]");
+  m.def("wgrad3_supported",
+        [](int64_t H, int64_t W, int64_t C, int64_t K) {
+          return bdbnn_wgrad3_supported((int)H, (int)W, (int)C, (int)K) !=
+                 0;
+        },
+        "shape predicate of the conv_wgrad3 route");
   m.def("repack_cplane", &repack_cplane,
         "activation sign bits -> padded per-channel u64 row planes");
   m.def("wgrad_finish", &wgrad_finish,

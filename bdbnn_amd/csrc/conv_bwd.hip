@@ -462,18 +462,7 @@ extern "C" void bdbnn_dgrad_wdec(const uint32_t* wp, const float* alpha,
 // Constraints: 3x3/s1/p1, C % 64 == 0, K % 64 == 0, W <= 64, g bf16
 // channels_last.
 
-#define WG2_CHUNK 128       // m entries per chunk
-#define WG2_BC 64           // c tile
-#define WG2_BK 64           // k tile
-
-struct Wgrad2Params {
-  int N, H, W, C, K;
-  int bands_per_image;      // ceil(H / RB)
-  int total_slots;          // N * bands_per_image
-  int total_chunks;         // ceil(total_slots / GB)
-  int split;                // chunk stride (== blocks per (c,k) tile)
-  int nh_rows;              // N * H  (xcp row count)
-};
+// (WG2_* tile constants, Wgrad2Params and the class table: conv_bwd_common.h)
 
 // Block geometry: each (c,k) tile is m-split over `split` blocks; a
 // block owns a CONTIGUOUS chunk range, so (for GB==1) consecutive
@@ -760,39 +749,6 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad2_kernel(
   // ---- m-split combine + plain coalesced slab store ----
   wgrad2_combine_store<9>(acc, red, dwT + (int64_t)split_id * 9 * p.C * p.K,
                           p.C, p.K, c0, k0, wid, lane);
-}
-
-// THE (WP, RB, GB) table of conv_wgrad2_kernel: calls f(BwdClass) for the
-// padded-width class of an (H, W) image.
-template <class F>
-static int wgrad2_class(int H, int W, F f) {
-  if (W <= 8 && H <= 8) return f(BwdClass<8, 8, 2>{});
-  if (W <= 16) return f(BwdClass<16, 8, 1>{});
-  if (W <= 32) return f(BwdClass<32, 4, 1>{});
-  return f(BwdClass<64, 2, 1>{});
-}
-
-static bool wgrad2_shape_ok(int W, int C, int K) {
-  return !(C % 64 || K % 64 || W > 64);
-}
-
-// chunking and m-split of a shape in class G.  The launcher and the
-// host-side slab count both take p.split from HERE: the kernel writes
-// exactly the slabs the caller allocated.
-template <class G>
-static Wgrad2Params wgrad2_params(G, int N, int H, int W, int C, int K) {
-  Wgrad2Params p;
-  p.N = N; p.H = H; p.W = W; p.C = C; p.K = K;
-  p.nh_rows = N * H;
-  p.bands_per_image = (H + G::RB - 1) / G::RB;
-  p.total_slots = N * p.bands_per_image;
-  p.total_chunks = (p.total_slots + G::GB - 1) / G::GB;
-  // LDS (~110-145 KB/block) admits ONE 512-thread block per CU: round
-  // the m-split so the grid is a whole multiple of 256 CUs (384 blocks
-  // = 1.5 dispatch rounds would idle half the chip for half the time)
-  int grid_ck = (C / WG2_BC) * (K / WG2_BK);
-  p.split = bd_min((256 + grid_ck - 1) / grid_ck, p.total_chunks);
-  return p;
 }
 
 // slab count (= split) for the host-side dwT allocation

@@ -1,5 +1,6 @@
 // Pieces shared by the MFMA backward kernels (conv_bwd.hip: stride 1,
-// conv_bwd_s2.hip: stride 2).
+// conv_bwd_s2.hip: stride 2, conv_wgrad3.hip: stride-1 wgrad from the
+// NHWC sign plane).
 #pragma once
 #include "common.h"
 #include "act_masks.h"
@@ -62,6 +63,55 @@ __device__ __forceinline__ void wgrad2_combine_store(
       }
     }
   }
+}
+
+// ---- geometry of the stride-1 wgrad kernels (conv_bwd.hip: wgrad2,
+// conv_wgrad3.hip: wgrad3), one table for both ----
+#define WG2_CHUNK 128       // m entries per chunk
+#define WG2_BC 64           // c tile
+#define WG2_BK 64           // k tile
+
+struct Wgrad2Params {
+  int N, H, W, C, K;
+  int bands_per_image;      // ceil(H / RB)
+  int total_slots;          // N * bands_per_image
+  int total_chunks;         // ceil(total_slots / GB)
+  int split;                // chunk stride (== blocks per (c,k) tile)
+  int nh_rows;              // N * H  (xcp row count)
+};
+
+// THE (WP, RB, GB) table of conv_wgrad2_kernel: calls f(BwdClass) for the
+// padded-width class of an (H, W) image.
+template <class F>
+static int wgrad2_class(int H, int W, F f) {
+  if (W <= 8 && H <= 8) return f(BwdClass<8, 8, 2>{});
+  if (W <= 16) return f(BwdClass<16, 8, 1>{});
+  if (W <= 32) return f(BwdClass<32, 4, 1>{});
+  return f(BwdClass<64, 2, 1>{});
+}
+
+static inline bool wgrad2_shape_ok(int W, int C, int K) {
+  return !(C % 64 || K % 64 || W > 64);
+}
+
+// chunking and m-split of a shape in class G.  The launcher and the
+// host-side slab count both take p.split from HERE: the kernel writes
+// exactly the slabs the caller allocated.
+template <class G>
+static Wgrad2Params wgrad2_params(G, int N, int H, int W, int C, int K) {
+  Wgrad2Params p;
+  p.N = N; p.H = H; p.W = W; p.C = C; p.K = K;
+  p.nh_rows = N * H;
+  p.bands_per_image = (H + G::RB - 1) / G::RB;
+  p.total_slots = N * p.bands_per_image;
+  p.total_chunks = (p.total_slots + G::GB - 1) / G::GB;
+  // LDS (wgrad2 ~140-159 KB, wgrad3 ~99-121 KB per block) admits ONE
+  // 512-thread block per CU: round
+  // the m-split so the grid is a whole multiple of 256 CUs (384 blocks
+  // = 1.5 dispatch rounds would idle half the chip for half the time)
+  int grid_ck = (C / WG2_BC) * (K / WG2_BK);
+  p.split = bd_min((256 + grid_ck - 1) / grid_ck, p.total_chunks);
+  return p;
 }
 
 // MODE: which activation-gradient mask the dgrad epilogue applies

@@ -41,6 +41,10 @@ _MFMA_BWD = os.environ.get("BDBNN_MFMA_BWD", "1") != "0"
 # csrc/conv_bwd_s2.hip) alone: BDBNN_MFMA_BWD_S2=0 sends just those convs
 # back to the MIOpen path while stride 1 stays on the owned kernels
 _MFMA_BWD_S2 = os.environ.get("BDBNN_MFMA_BWD_S2", "1") != "0"
+# the stride-1 weight gradient straight from the NHWC sign plane
+# (csrc/conv_wgrad3.hip, default ON); BDBNN_WGRAD3=0 keeps repack_cplane +
+# conv_wgrad2, its A/B partner
+_WGRAD3 = os.environ.get("BDBNN_WGRAD3", "1") != "0"
 
 
 def _act_grad_mask(x: torch.Tensor, mode: str, t, k) -> torch.Tensor:
@@ -83,9 +87,10 @@ def _owned_backward(nat, route, g, w, xp, wp, alpha, C, mode, mp, x, t, k,
     bitplane mp; 1/2: value mask of the saved activation x).  dgrad: halo
     (s1) / parity-phase (s2) implicit GEMM with the mask and the deferred
     skip grad, if any, in its epilogue.  wgrad: all-tap block GEMM straight
-    from the sign BITS, repacked per channel (the dense +-1 activation is
-    never materialized), then slab sum + transpose + |w|<=1 mask in one
-    pass."""
+    from the sign BITS (the dense +-1 activation is never materialized):
+    stride 1 reads the NHWC sign plane as saved (conv_wgrad3), stride 2 and
+    the BDBNN_WGRAD3=0 path a per-channel repack of it; then slab sum +
+    transpose + |w|<=1 mask in one pass."""
     s2 = route == "s2"
     H, W, ks = xp.shape[1], xp.shape[2], w.shape[2]
     wd = (nat.dgrad_weight_decode_1x1 if ks == 1
@@ -98,8 +103,11 @@ def _owned_backward(nat, route, g, w, xp, wp, alpha, C, mode, mp, x, t, k,
     else:
         dx = (nat.conv_dgrad2(g, wd, mp, C, acc) if mode == 0
               else nat.conv_dgrad2_x(g, wd, x, C, mode, t, k, acc))
-        planes = nat.repack_cplane(xp, C, W)
-        dwT = nat.conv_wgrad2(g, planes, C)
+        if _WGRAD3 and nat.wgrad3_supported(H, W, C, w.shape[0]):
+            dwT = nat.conv_wgrad3(g, xp, C)
+        else:
+            planes = nat.repack_cplane(xp, C, W)
+            dwT = nat.conv_wgrad2(g, planes, C)
         dw = nat.wgrad_finish(dwT, w.float())
     return dx, dw
 
