@@ -211,6 +211,24 @@ int bdbnn_wgrad3_nslab(int N, int H, int W, int C, int K);
 int bdbnn_conv_wgrad3(const void* g, const uint32_t* xp, float* dwT, int N,
                       int H, int W, int C, int K, hipStream_t stream);
 
+// ---- conv_bwd_small.hip (3x3/s1/p1 MFMA backward, C and K in {16, 32},
+// W <= 64; the contracts of conv_dgrad2 and conv_wgrad3) ----
+// shape can run AND its class is routed here by default
+int bdbnn_bwd_small_supported(int H, int W, int C, int K);
+// 0 launched, -1 unsupported shape, -2 too large for int pixel indices,
+// -3 bad mode
+int bdbnn_conv_dgrad_small(const void* g, const void* wd, const uint32_t* mp,
+                           const void* x, void* dx, const void* accp,
+                           int mode, float t, float k, int N, int H, int W,
+                           int C, int K, hipStream_t stream);
+int bdbnn_wgrad_small_nslab(int N, int H, int W, int C, int K);
+int bdbnn_conv_wgrad_small(const void* g, const uint32_t* xp, float* dwT,
+                           int N, int H, int W, int C, int K,
+                           hipStream_t stream);
+// slab-parallel sum of slabs [nslab][9][C][K] into out [9][C][K]
+void bdbnn_wgrad_small_fold(const float* slabs, float* out, int nslab, int C,
+                            int K, hipStream_t stream);
+
 // ---- conv_bwd_s2.hip (3x3/s2/p1 and 1x1/s2/p0 MFMA backward) ----
 int bdbnn_s2_kernels_can_run(int H, int W, int C, int K, int ks);
 int bdbnn_dgrad2_s2_supported(int H, int W, int C, int K, int ks);

@@ -1135,8 +1135,9 @@ static at::Tensor dgrad_wdec_impl(const at::Tensor& wp,
               who, ": wp must be packed ", ks, "x", ks,
               " weights [K][ks][ks][CW] int32");
   int K = (int)wp.size(0);
-  TORCH_CHECK(K % 8 == 0 && C % 32 == 0 && wp.size(3) == C / 32, who,
-              ": C must match wp (K%8, C%32)");
+  TORCH_CHECK(K % 8 == 0 && (C % 32 == 0 || C == 16) &&
+                  wp.size(3) == (C + 31) / 32,
+              who, ": C must match wp (K%8, C%32 or C = 16)");
   TORCH_CHECK(alpha.is_cuda() && alpha.scalar_type() == at::kFloat &&
                   alpha.numel() == K,
               who, ": alpha must be fp32 [K]");
@@ -1322,6 +1323,87 @@ at::Tensor conv_wgrad3(const at::Tensor& g, const at::Tensor& xp,
                              cur_stream());
   TORCH_CHECK(rc == 0, "conv_wgrad3: launch rejected the shape");
   return dwT;
+}
+
+// ---------------- stride 1, C and K in {16, 32} (conv_bwd_small.hip) -----
+
+// conv_dgrad2's dx for the 16/32-channel convs: mode 0 masks with the
+// bitplane mp ([N][H][W][1], bits c < C), modes 1/2 with the value mask of
+// the saved activation x
+at::Tensor conv_dgrad_small(const at::Tensor& g, const at::Tensor& wd,
+                            int64_t C, int64_t mode,
+                            const c10::optional<at::Tensor>& mp,
+                            const c10::optional<at::Tensor>& x, double t,
+                            double k, const c10::optional<at::Tensor>& acc) {
+  const char* who = "conv_dgrad_small";
+  check_grad_bf16_cl(g, who);
+  int64_t N = g.size(0), K = g.size(1), H = g.size(2), W = g.size(3);
+  TORCH_CHECK((C == 16 || C == 32) && (K == 16 || K == 32) && W <= 64 &&
+                  H <= (1 << 20) && N * H * W < (int64_t(1) << 31),
+              who, ": unsupported shape (C, K in {16, 32}, W <= 64)");
+  TORCH_CHECK(wd.is_cuda() && wd.dim() == 3 && wd.size(0) == 9 &&
+                  wd.size(1) == C && wd.size(2) == K &&
+                  wd.scalar_type() == at::kBFloat16 && wd.is_contiguous(),
+              who, ": decoded weights [9][C][K] bf16");
+  TORCH_CHECK(mode >= 0 && mode <= 2, who,
+              ": mode must be 0 (clip-STE), 1 (approx) or 2 (EDE)");
+  const uint32_t* mp_ptr = nullptr;
+  const void* x_ptr = nullptr;
+  if (mode == 0) {
+    TORCH_CHECK(mp.has_value() && !x.has_value(), who,
+                ": mode 0 needs mp and x=None");
+    TORCH_CHECK(mp->is_cuda() && mp->scalar_type() == at::kInt &&
+                    mp->is_contiguous() && mp->size(-1) == 1 &&
+                    mp->numel() == N * H * W,
+                who, ": mp must be the int32 mask bitplane [N,H,W,1]");
+    mp_ptr = (const uint32_t*)mp->data_ptr<int>();
+  } else {
+    TORCH_CHECK(x.has_value() && !mp.has_value(), who,
+                ": modes 1/2 need x and mp=None");
+    check_act_bf16_cl(*x, N, C, H, W, who);
+    x_ptr = x->data_ptr();
+  }
+  at::Tensor ac = acc_as_bf16_cl(acc, N, C, H, W, who);
+  auto dx = empty_dx(g, N, C, H, W);
+  int rc = bdbnn_conv_dgrad_small(
+      g.data_ptr(), wd.data_ptr(), mp_ptr, x_ptr, dx.data_ptr(),
+      ac.defined() ? ac.data_ptr() : nullptr, (int)mode, (float)t, (float)k,
+      (int)N, (int)H, (int)W, (int)C, (int)K, cur_stream());
+  TORCH_CHECK(rc == 0, who, ": launch rejected the shape");
+  return dx;
+}
+
+// conv_wgrad3's slabs for the 16/32-channel convs, from the NHWC sign
+// plane xp [N][H][W][1].  fold: more than 8 block slabs are summed into one
+// by a slab-parallel pass before they are returned (wgrad_finish walks the
+// slabs serially); fold = false returns the block slabs as written.
+at::Tensor conv_wgrad_small(const at::Tensor& g, const at::Tensor& xp,
+                            int64_t C, bool fold) {
+  const char* who = "conv_wgrad_small";
+  check_grad_bf16_cl(g, who);
+  int64_t N = g.size(0), K = g.size(1), H = g.size(2), W = g.size(3);
+  TORCH_CHECK((C == 16 || C == 32) && (K == 16 || K == 32) && W <= 64 &&
+                  H <= (1 << 20) && N * H * W < (int64_t(1) << 31),
+              who, ": unsupported shape (C, K in {16, 32}, W <= 64)");
+  TORCH_CHECK(xp.is_cuda() && xp.dim() == 4 &&
+                  xp.scalar_type() == at::kInt && xp.is_contiguous() &&
+                  xp.size(0) == N && xp.size(1) == H && xp.size(2) == W &&
+                  xp.size(3) == 1,
+              who, ": xp must be contiguous int32 [N][H][W][1]");
+  int nslab = bdbnn_wgrad_small_nslab((int)N, (int)H, (int)W, (int)C, (int)K);
+  TORCH_CHECK(nslab > 0, who, ": unsupported shape");
+  // per-block partial slabs; every word is written (no memset)
+  auto dwT = at::empty({nslab, 9, C, K}, g.options().dtype(at::kFloat));
+  int rc = bdbnn_conv_wgrad_small(g.data_ptr(),
+                                  (const uint32_t*)xp.data_ptr<int>(),
+                                  dwT.data_ptr<float>(), (int)N, (int)H,
+                                  (int)W, (int)C, (int)K, cur_stream());
+  TORCH_CHECK(rc == 0, who, ": launch rejected the shape");
+  if (!fold || nslab <= 8) return dwT;
+  auto one = at::empty({1, 9, C, K}, dwT.options());
+  bdbnn_wgrad_small_fold(dwT.data_ptr<float>(), one.data_ptr<float>(), nslab,
+                         (int)C, (int)K, cur_stream());
+  return one;
 }
 
 // ---------------- stride 2 (3x3/s2/p1, 1x1/s2/p0) ----------------
@@ -1655,6 +1737,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "activation sign bits -> padded per-channel u64 row planes");
   m.def("wgrad_finish", &wgrad_finish,
         "dwT transpose to [K][C][3][3] + |w|<=1 STE mask, one pass");
+  m.def("conv_dgrad_small", &conv_dgrad_small,
+        "MFMA bf16 dgrad of a 3x3/s1/p1 binary conv with C and K in "
+        "{16, 32} (wd [9][C][K]); mode 0 masks with the bitplane mp, modes "
+        "1/2 with the value mask of x; optional acc adds a same-shape "
+        "skip-gradient tensor in the epilogue",
+        py::arg("g"), py::arg("wd"), py::arg("C"), py::arg("mode"),
+        py::arg("mp"), py::arg("x"), py::arg("t"), py::arg("k"),
+        py::arg("acc") = py::none());
+  m.def("conv_wgrad_small", &conv_wgrad_small,
+        "MFMA bf16 wgrad of a 3x3/s1/p1 binary conv with C and K in "
+        "{16, 32} from the NHWC sign plane -> fp32 [nslab][9][C][K]; more "
+        "than 8 block slabs come back summed into one unless fold is false",
+        py::arg("g"), py::arg("xp"), py::arg("C"), py::arg("fold") = true);
+  m.def("bwd_small_supported",
+        [](int64_t H, int64_t W, int64_t C, int64_t K) {
+          return H >= 1 && W >= 1 && H <= (1 << 20) && W <= (1 << 20) &&
+                 C <= (1 << 20) && K <= (1 << 20) &&
+                 bdbnn_bwd_small_supported((int)H, (int)W, (int)C,
+                                           (int)K) != 0;
+        },
+        "routing predicate of conv_dgrad_small / conv_wgrad_small: "
+        "3x3/s1/p1 with C and K both in {16, 32}, W <= 64",
+        py::arg("H"), py::arg("W"), py::arg("C"), py::arg("K"));
   m.def("dgrad2_s2_supported",
         [](int64_t H, int64_t W, int64_t C, int64_t K, int64_t ks) {
           return dgrad2_s2_routed(H, W, C, K, ks);

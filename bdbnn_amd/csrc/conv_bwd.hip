@@ -432,10 +432,10 @@ extern "C" void bdbnn_dgrad_wdec(const uint32_t* wp, const float* alpha,
   int blocks = (int)bd_min<int64_t>((total + 255) / 256, 4096);
   if (nt == 9)
     dgrad_wdec_kernel<9><<<blocks, 256, 0, stream>>>(wp, alpha, (__bf16*)wd,
-                                                     C, K, C / 32);
+                                                     C, K, (C + 31) / 32);
   else
     dgrad_wdec_kernel<1><<<blocks, 256, 0, stream>>>(wp, alpha, (__bf16*)wd,
-                                                     C, K, C / 32);
+                                                     C, K, (C + 31) / 32);
 }
 
 // ======================= wgrad v2 =======================

@@ -1,6 +1,6 @@
 // Pieces shared by the MFMA backward kernels (conv_bwd.hip: stride 1,
 // conv_bwd_s2.hip: stride 2, conv_wgrad3.hip: stride-1 wgrad from the
-// NHWC sign plane).
+// NHWC sign plane, conv_bwd_small.hip: stride 1 at 16/32 channels).
 #pragma once
 #include "common.h"
 #include "act_masks.h"

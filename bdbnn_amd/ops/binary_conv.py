@@ -45,6 +45,10 @@ _MFMA_BWD_S2 = os.environ.get("BDBNN_MFMA_BWD_S2", "1") != "0"
 # (csrc/conv_wgrad3.hip, default ON); BDBNN_WGRAD3=0 keeps repack_cplane +
 # conv_wgrad2, its A/B partner
 _WGRAD3 = os.environ.get("BDBNN_WGRAD3", "1") != "0"
+# the 16/32-channel stride-1 kernels of that backward (the first two stages
+# of CIFAR ResNet-20, csrc/conv_bwd_small.hip) alone: BDBNN_MFMA_BWD_SMALL=0
+# sends just those convs back to the MIOpen path
+_MFMA_BWD_SMALL = os.environ.get("BDBNN_MFMA_BWD_SMALL", "1") != "0"
 
 
 def _act_grad_mask(x: torch.Tensor, mode: str, t, k) -> torch.Tensor:
@@ -65,9 +69,11 @@ def _act_grad_mask(x: torch.Tensor, mode: str, t, k) -> torch.Tensor:
 def _owned_route(nat, *, g_dtype, x_dtype, stride, padding, ks, H_in, W_in,
                  H_out, W_out, C, K, mask_mode, valmask):
     """Which owned MFMA backward runs a binary conv: "s1" (3x3/s1/p1,
-    csrc/conv_bwd.hip), "s2" (3x3/s2/p1 and 1x1/s2/p0, csrc/conv_bwd_s2.hip)
-    or None (MIOpen on decoded operands).  The whole routing decision:
-    knobs, dtypes, geometry, and the native shape predicates.  ks is the
+    csrc/conv_bwd.hip), "s1small" (3x3/s1/p1 with C and K in {16, 32},
+    csrc/conv_bwd_small.hip), "s2" (3x3/s2/p1 and 1x1/s2/p0,
+    csrc/conv_bwd_s2.hip) or None (MIOpen on decoded operands).  The whole
+    routing decision: knobs, dtypes, geometry, and the native shape
+    predicates.  ks is the
     (square) kernel size; a value-mask context that carries the clip-STE
     mask (mask_mode 0) has no owned kernel."""
     if not _MFMA_BWD or (valmask and mask_mode == 0):
@@ -75,7 +81,11 @@ def _owned_route(nat, *, g_dtype, x_dtype, stride, padding, ks, H_in, W_in,
     if g_dtype != torch.bfloat16 or x_dtype != torch.bfloat16:
         return None
     if (ks, stride, padding) == (3, 1, 1):
-        return "s1" if nat.dgrad2_supported(H_out, W_out, C, K) else None
+        if nat.dgrad2_supported(H_out, W_out, C, K):
+            return "s1"
+        if _MFMA_BWD_SMALL and nat.bwd_small_supported(H_out, W_out, C, K):
+            return "s1small"
+        return None
     if _MFMA_BWD_S2 and stride == 2 and (ks, padding) in ((3, 1), (1, 0)):
         return "s2" if nat.dgrad2_s2_supported(H_in, W_in, C, K, ks) else None
     return None
@@ -88,9 +98,9 @@ def _owned_backward(nat, route, g, w, xp, wp, alpha, C, mode, mp, x, t, k,
     (s1) / parity-phase (s2) implicit GEMM with the mask and the deferred
     skip grad, if any, in its epilogue.  wgrad: all-tap block GEMM straight
     from the sign BITS (the dense +-1 activation is never materialized):
-    stride 1 reads the NHWC sign plane as saved (conv_wgrad3), stride 2 and
-    the BDBNN_WGRAD3=0 path a per-channel repack of it; then slab sum +
-    transpose + |w|<=1 mask in one pass."""
+    stride 1 reads the NHWC sign plane as saved (conv_wgrad3,
+    conv_wgrad_small), stride 2 and the BDBNN_WGRAD3=0 path a per-channel
+    repack of it; then slab sum + transpose + |w|<=1 mask in one pass."""
     s2 = route == "s2"
     H, W, ks = xp.shape[1], xp.shape[2], w.shape[2]
     wd = (nat.dgrad_weight_decode_1x1 if ks == 1
@@ -100,6 +110,10 @@ def _owned_backward(nat, route, g, w, xp, wp, alpha, C, mode, mp, x, t, k,
         planes = nat.repack_cplane_s2(xp, C, H, W)
         dwT = nat.conv_wgrad2_s2(g, planes, C, H, W, ks)
         dw = nat.wgrad_finish_s2(dwT, w.float())
+    elif route == "s1small":
+        dx = nat.conv_dgrad_small(g, wd, C, mode, mp, x, t, k, acc)
+        dwT = nat.conv_wgrad_small(g, xp, C)
+        dw = nat.wgrad_finish(dwT, w.float())
     else:
         dx = (nat.conv_dgrad2(g, wd, mp, C, acc) if mode == 0
               else nat.conv_dgrad2_x(g, wd, x, C, mode, t, k, acc))

@@ -28,6 +28,7 @@ sources = [os.path.join(CSRC, f) for f in (
     "loss.hip",
     "conv_bwd.hip",
     "conv_bwd_s2.hip",
+    "conv_bwd_small.hip",
     "conv_wgrad3.hip",
     "stem_conv.hip",
     "xnor_conv.hip",
